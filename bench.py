@@ -17,7 +17,13 @@ scaling) and every step ends with the B&B round's exchanges over RCCL: the incum
 all-reduce(MAX) and the all-gather of the round's new cut rows (shards.py); the
 per-step time is the max over ranks.
 
-Beside the headline the line carries: `parity` (the timed step's results for the first
+A plain run does only what the headline needs: it sets up, warms up, times --steps steps,
+writes the last timed step's outputs when --dump-outputs DIR is given (DIR/<name>.npy, float32 /
+float64: results, DD sizes, cutset children and argmax paths as the engine's caller receives them;
+the inputs are seeded, so two builds can be compared output for output) and prints the line.
+Everything below runs only with --full.
+
+With --full the line carries beside the headline: `parity` (the timed step's results for the first
 --cpu-sample records against the reference's own RelaxedDDNew on the same records, bit for
 bit), `cpu_baseline` (that reference run's rate on the host cores), `roofline` (PMC-counted
 HBM bytes of this build per k_relax launch, with the issue counters of the same build),
@@ -31,7 +37,7 @@ search strong-scaled over the N frontier shards (incumbent all-reduce, cut-row a
 work sharing every round; through the library's own RCCL communicator, shard.cpp, when the
 backend is nccl).  Progress goes to stderr; stdout carries the one JSON line.
 
-Launch: python bench.py [--gpus N --steps K --warmup W]; for N > 1 the driver uses
+Launch: python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]; for N > 1 the driver uses
 torch.distributed.run and this script reads RANK / LOCAL_RANK / WORLD_SIZE.
 """
 from __future__ import annotations
@@ -59,6 +65,11 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also run every other leg (CPU baseline and parity against the "
+                         "reference, subproblem, B&B, bnb_parity, config-5 and multi-rank B&B legs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the arrays the last timed step computed to DIR/<name>.npy")
     ap.add_argument("--nodes", type=int, default=8192, help="open nodes per GPU per step")
     ap.add_argument("--config", default="C4")
     ap.add_argument("--seed", type=int, default=1)
@@ -547,6 +558,52 @@ def heartbeat(tag="bench", every=30.0):
     threading.Thread(target=run, daemon=True).start()
 
 
+DUMP_BUDGET_BYTES = 60 * 2**20   # all of --dump-outputs stays below 64 MB
+
+
+def dump_outputs(out_dir, eng, results, stats):
+    """--dump-outputs: what a caller of the timed path receives after the last timed step, one
+    DIR/<name>.npy per array: the per-record results and DD sizes, the cutset children (the
+    frontier records the step wrote) and the argmax paths of the exact DDs.  Bounds and offsets
+    go out as float64, the small integers (status, flags, layers, states, arc ids) as float32,
+    both exact.  An array without elements is not written (its offsets array tells that it is
+    empty).  The arrays are written whole while they fit the budget; a larger one is cut to
+    a fixed sample (sorted indices from a generator seeded by the array's position in the list
+    and its length), so two builds that agree write the same files."""
+    st, ex, lb, ub, nc = results
+    dn, da, dl, sw = stats
+    child_off, cgl, clb, cub, soff, states, poff, sol = eng.children_arrays()
+    p_off, pbuf = eng.paths()
+    arrays = [("status", st, np.float32), ("exact", ex, np.float32), ("lb", lb, np.float64), ("ub", ub, np.float64),
+              ("n_children", nc, np.float32), ("dd_nodes", dn, np.float64), ("dd_arcs", da, np.float64),
+              ("dd_layers", dl, np.float32), ("sweeps", sw, np.float32),
+              ("child_off", child_off, np.float64), ("child_gl", cgl, np.float32), ("child_lb", clb, np.float64),
+              ("child_ub", cub, np.float64), ("child_states_off", soff, np.float64),
+              ("child_states", states[:int(soff[-1])] if len(soff) else states[:0], np.float32),
+              ("child_sol_off", poff, np.float64),
+              ("child_sol", sol[:int(poff[-1])] if len(poff) else sol[:0], np.float32),
+              ("path_off", p_off, np.float64), ("path", pbuf[:int(p_off[-1])] if len(p_off) else pbuf[:0], np.float32)]
+    os.makedirs(out_dir, exist_ok=True)
+    # smallest first: each array may take an equal share of what the ones before it left
+    order = sorted(range(len(arrays)), key=lambda i: arrays[i][1].size * np.dtype(arrays[i][2]).itemsize)
+    left = DUMP_BUDGET_BYTES
+    for pos, i in enumerate(order):
+        name, a, dt = arrays[i]
+        if a.size == 0:
+            # nothing to compare (no exact DD in the batch: no argmax path); its offsets say so
+            stale = os.path.join(out_dir, name + ".npy")
+            if os.path.exists(stale):
+                os.remove(stale)
+            continue
+        cap = (left // (len(order) - pos)) // np.dtype(dt).itemsize
+        if a.size > cap:
+            idx = np.sort(np.random.default_rng([i, a.size]).choice(a.size, size=cap, replace=False))
+            a = a[idx]
+        a = np.ascontiguousarray(a, dtype=dt)
+        left -= a.nbytes
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def main():
     args = parse()
     if args.mode == "bnb":
@@ -653,11 +710,14 @@ def main():
 
     total_nodes = mine.n * world
     value = total_nodes * args.steps / elapsed
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, eng, (st, ex, lb, ub, nc), (dn, da, dl, sw))
+    legs = args.full      # everything beside the headline runs only with --full
     gpu_sample = None
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if legs and rank == 0 and world == 1 and not args.no_cpu:
         k = min(args.cpu_sample, mine.n)
         gpu_sample = eng._collect()[:k]          # the last timed step's results, record order
-    sub = subproblem_leg(eng, inst, net, args) if rank == 0 else None
+    sub = subproblem_leg(eng, inst, net, args) if legs and rank == 0 else None
     line = {
         "metric": METRIC,
         "value": round(value, 2),
@@ -711,7 +771,7 @@ def main():
     }
     if comm is not None:
         line["exchange_bytes_per_step"] = round((comm.bytes - bytes0) / args.steps, 1)
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if legs and rank == 0 and world == 1 and not args.no_cpu:
         cb, par = cpu_baseline(work, net, pool, mine, incumbent, args, gpu_sample)
         line["cpu_baseline"] = cb
         line["parity"] = par
@@ -723,7 +783,7 @@ def main():
         sub.pop("_inst0", None)
         sub["counters"] = sub_profile_block(args.profile_tag)
     eng.close()
-    if rank == 0 and world == 1 and args.bnb_leg_seconds > 0:
+    if legs and rank == 0 and world == 1 and args.bnb_leg_seconds > 0:
         # BASELINE metric with the subproblems in the loop: the device B&B on the same
         # 1k-arc network with its 256 scenarios (lower bounds 0: feasible, optimality cuts)
         line["bnb"] = bnb_run(args.config, args.seed, "zero", args.bnb_leg_seconds, 1024, args.round_seconds, work,
@@ -744,11 +804,11 @@ def main():
             # first one's ray as a feasibility cut (grb.cpp:284-351) in the loop
             line["bnb_gen"] = bnb_run(args.config, args.seed, "gen", args.bnb_gen_seconds, 1024, args.round_seconds,
                                       work, device=local, progress=0.0, tag="legg", heuristic=args.bnb_seeded_width)
-    if rank == 0 and world == 1 and args.bnb_parity_rounds > 0:
+    if legs and rank == 0 and world == 1 and args.bnb_parity_rounds > 0:
         line["bnb_parity"] = bnb_parity_leg(args)
-    if rank == 0 and world == 1 and args.config == "C4" and args.c5_nodes > 0:
+    if legs and rank == 0 and world == 1 and args.config == "C4" and args.c5_nodes > 0:
         line["config5"] = config5_leg(args, work)
-    if world > 1 and args.bnb_leg_seconds > 0:
+    if legs and world > 1 and args.bnb_leg_seconds > 0:
         # BASELINE configs[3]: one search shared by the N frontier shards (strong scaling), the
         # round exchanges over the library's own RCCL communicator -- beside the weak-scaling
         # relaxation step above.  A watchdog prints the line without this leg should a shard
