@@ -209,24 +209,18 @@ __device__ __forceinline__ double vmin64(double a, double b) {
 }
 
 // ancestors of leaf j (wave-local) from layer dj down to the leaf's parent, values in vb;
-// returns the parent value
-#ifndef SGUFP_LEAF_INFOREG
-#define SGUFP_LEAF_INFOREG 1   // the walk's per-layer info bytes from registers (v_readlane), not LDS
-#endif
+// returns the parent value.  The walk's per-layer info bytes come from registers (v_readlane),
+// not LDS
 template <class LeafShared>
 __device__ __forceinline__ double walk_down(LeafShared &S, int w, int j, int dj, int T, int us, double root, uint32_t ilo,
                                             uint32_t ihi) {
     double prev = (dj <= 1) ? root : S.vb[w][dj - 1][lane()];
     for (int k = dj; k < T - 1; k++) {
-#if SGUFP_LEAF_INFOREG
         static_assert(kExactMaxT <= 9, "layers 1-8 in two packed words");
         // lane j packs leaf j's info bytes of layers 1-4 (ilo) and 5-7 (ihi): a scalar read with
         // no LDS round trip before the coefficient's
         const uint32_t src = k <= 4 ? ilo : ihi;
         const uint32_t b = ((uint32_t)__builtin_amdgcn_readlane((int)src, j) >> (8 * ((k - 1) & 3))) & 0xFFu;
-#else
-        const uint32_t b = uni((uint32_t)S.lw[w].info[j][k]);
-#endif
         const uint32_t r = b & 63u;
         const double x = !(b & 128u) ? EDMIN : (r ? prev + S.C[(k - 1) * us + r][lane()] : prev);
         S.vb[w][k][lane()] = x;
@@ -260,25 +254,6 @@ __device__ double first_zero(const NetDev &net, const ExactIO &ex, LeafShared &S
     return 0.0;
 }
 
-#ifndef SGUFP_LEAF_REGS
-#define SGUFP_LEAF_REGS 0   // 1: ancestor values in registers (spills at the 6-wave bound; measured slower)
-#endif
-#ifndef SGUFP_LEAF_PIPE
-#define SGUFP_LEAF_PIPE 1   // the next cut block's coefficients load while this one is swept
-#endif
-#ifndef SGUFP_LEAF_ROWMASK
-#define SGUFP_LEAF_ROWMASK 1   // stage only the rows the pass's leaves add (0: all rows, A/B)
-#endif
-#ifndef SGUFP_LEAF_BALANCE
-#define SGUFP_LEAF_BALANCE 1   // a pass's leaves split evenly over its eight waves
-#endif
-#ifndef SGUFP_LEAF_FAST
-#define SGUFP_LEAF_FAST 0   // 1: exact entries with lazy walks, mask tests, row offsets (measured: no gain)
-#endif
-#ifndef SGUFP_LEAF_LASTREG
-#define SGUFP_LEAF_LASTREG 0   // 1: the last layer's rows of a block in registers (measured slower)
-#endif
-constexpr int kLastRegs = 4;   // ranks 1 .. 4 (C3 / C4 trees: 3; higher ranks read LDS)
 #ifndef SGUFP_LEAF_MIN_WAVES
 #define SGUFP_LEAF_MIN_WAVES 6   // three 8-wave workgroups per CU (VGPRs <= 85)
 #endif
@@ -363,18 +338,13 @@ __global__ void __launch_bounds__(kLeafWaves * kWave, SGUFP_LEAF_MIN_WAVES) k_ex
             S.stab[e] = r == 0 ? -1 : slot_of(net, g, len, aligned, kb + k, r);
         }
         // this wave's leaves: ancestry tables and alive mask.  A pass's n leaves are split into
-        // eight runs of ceil(n / 8) consecutive leaves (not 16 for the first waves and none for the
-        // rest): a partial pass -- every record's last one, and phase B's open lists are mostly
-        // short -- keeps all waves busy, and each barrier waits for ceil(n / 8) leaves, not 16
-#if SGUFP_LEAF_BALANCE
+        // eight runs of ceil(n / 8) consecutive leaves, so that a partial pass -- every record's
+        // last one, and phase B's open lists are mostly short -- keeps all waves busy, and each
+        // barrier waits for ceil(n / 8) leaves, not for a full wave of 16
         const int npass = min(kLeafPass, (pb ? nopen : (int)lnn) - pass * kLeafPass);
         const int per = (npass + kLeafWaves - 1) / kLeafWaves;
         const int j0 = pass * kLeafPass + w * per;
         const int cnt = uni(max(0, min(per, npass - w * per)));
-#else
-        const int j0 = pass * kLeafPass + w * kLeavesPerWave;
-        const int cnt = uni(max(0, min(kLeavesPerWave, (pb ? nopen : (int)lnn) - j0)));
-#endif
         // lane j's leaf (index among the record's leaves): consecutive in phase A, from the open
         // list in phase B (in the order phase A's passes appended them)
         const int lid = lane() < cnt ? (pb ? olist[j0 + lane()] : j0 + lane()) : 0;
@@ -419,7 +389,6 @@ __global__ void __launch_bounds__(kLeafWaves * kWave, SGUFP_LEAF_MIN_WAVES) k_ex
         }
         // leaf j's info bytes in lane j's registers (walk_down reads them with v_readlane)
         uint32_t ilo = 0, ihi = 0;
-#if SGUFP_LEAF_INFOREG
         if (lane() < kLeavesPerWave) {
 #pragma unroll
             for (int k = 1; k < kExactMaxT; k++) {
@@ -430,7 +399,6 @@ __global__ void __launch_bounds__(kLeafWaves * kWave, SGUFP_LEAF_MIN_WAVES) k_ex
                 }
             }
         }
-#endif
         __syncthreads();
         // per leaf, in scalar registers for the whole pass: 16 bits = the LDS row of its
         // last-layer coefficient (bits 0-6; kRowNoAdd: a -1 decision, kRowDead: in-arc dead) |
@@ -444,14 +412,6 @@ __global__ void __launch_bounds__(kLeafWaves * kWave, SGUFP_LEAF_MIN_WAVES) k_ex
             const uint32_t row = !(b & 128u) ? kRowDead : (r ? (uint32_t)((T - 2) * us) + r : kRowNoAdd);
             lp = row | (uint32_t)S.lw[w].dv[lane()] << 8;
         }
-#if SGUFP_LEAF_FAST
-        // exact entries' leaf loop (below): per pass, wave-uniform masks of the leaves that start a
-        // walk (a new parent) and of the leaves whose last arc adds nothing (dead in-arc, -1
-        // decision), and per leaf the byte offset of its coefficient row in S.C
-        const uint32_t walkm = uni((uint32_t)__ballot(lane() < cnt && (lane() == 0 || (int)(lp >> 8) < T - 1)));
-        const uint32_t specm = uni((uint32_t)__ballot(lane() < cnt && (lp & 0x7Fu) >= kRowDead));
-        const uint32_t lpo = (lp & 0x7Fu) < kRowDead ? (lp & 0x7Fu) * (uint32_t)(kWave * sizeof(double)) : 0u;
-#endif
         double m[kLeavesPerWave];
 #pragma unroll
         for (int j = 0; j < kLeavesPerWave; j++) m[j] = EDMAX;
@@ -482,7 +442,6 @@ __global__ void __launch_bounds__(kLeafWaves * kWave, SGUFP_LEAF_MIN_WAVES) k_ex
         const int bsplit = split ? min(nlim, ex.leaf_split) : nlim;
         if (pb) bfrom = bsplit;
         const int bend = ph2 ? bto + 1 : (split && !pb ? bsplit : nlim);
-#if SGUFP_LEAF_PIPE
         // a block's coefficients are loaded into registers while the previous block is swept
         // (every load of a block issued at once), stored to LDS at the top of its iteration --
         // the end of the previous iteration's barriers found every wave done with the old ones.
@@ -494,12 +453,8 @@ __global__ void __launch_bounds__(kLeafWaves * kWave, SGUFP_LEAF_MIN_WAVES) k_ex
         double stg[kSU];
         int srow[kSU], sslot[kSU];
         {
-            // (a used row with no coefficient slot is staged as zeros, as before)
-#if SGUFP_LEAF_ROWMASK
+            // (a used row with no coefficient slot is staged as zeros)
             uint64_t mm = (uint64_t)S.rmask[0] | (uint64_t)S.rmask[1] << 32;
-#else
-            uint64_t mm = E >= 64 ? ~0ull : (1ull << E) - 1ull;   // A/B: every row of the tree
-#endif
             // the (w + 8 u)-th set bit of mm for u = 0 .. kSU - 1 (uniform scalar walk, once a pass)
             for (int c = 0; c < w && mm; c++) mm &= mm - 1;
 #pragma unroll
@@ -522,7 +477,6 @@ __global__ void __launch_bounds__(kLeafWaves * kWave, SGUFP_LEAF_MIN_WAVES) k_ex
                 stg[u] = (sslot[u] >= 0 && sx < ncx) ? cmx[(size_t)sslot[u] * csx + (scrx ? sx : ncx - 1 - sx)] : 0.0;
         };
         if (bfrom < bend) stage_load(bfrom);
-#endif
 #ifdef SGUFP_LEAF_CLOCKS
         // diagnostics build: per wave the cycles of (staging + first barrier, leaf loop, the rest)
         uint64_t ck[3] = {0, 0, 0}, ct = clock64();
@@ -536,37 +490,16 @@ __global__ void __launch_bounds__(kLeafWaves * kWave, SGUFP_LEAF_MIN_WAVES) k_ex
             const bool scr = bb < nbs_r;
             const int b = scr ? bb : bb - nbs_r;
             const int ncut = scr ? ex.nsc : ex.no;
-#if SGUFP_LEAF_PIPE
 #pragma unroll
             for (int u = 0; u < kSU; u++)
                 if (srow[u] >= 0) S.C[srow[u]][lane()] = stg[u];
             __syncthreads();
             LEAF_CK(0);
             if (bb + 1 < bend) stage_load(bb + 1);
-#else
-            const GBL double *cm = scr ? ex.coefS : ex.coefO;
-            const size_t cs = scr ? (size_t)kExactScreen : (size_t)ex.ostride;
-            // stage the block's coefficients: row e = (layer, rank), lane = cut
-            for (int x = tid; x < E * kWave; x += kLeafWaves * kWave) {
-                const int e = x >> 6, l = x & (kWave - 1);
-                const int s = b * kWave + l;
-                const int sl = S.stab[e];
-                S.C[e][l] = (sl >= 0 && s < ncut) ? cm[(size_t)sl * cs + (scr ? s : ncut - 1 - s)] : 0.0;
-            }
-            __syncthreads();
-#endif
             const int s = b * kWave + lane();
             const bool vc = s < ncut && s >= first;
             double ms = -INFINITY;   // non-exact: max over this wave's alive leaves, this lane's cut
             if (cnt > 0 && (nx || (done & alive) != alive)) {
-#if SGUFP_LEAF_LASTREG
-                // the last layer's rows (ranks 1 .. kLastRegs) of this block in registers, read once:
-                // a leaf's own coefficient is then a select, not an LDS round trip per leaf
-                const int lrow1 = (T - 2) * us + 1;
-                double cl[kLastRegs];
-#pragma unroll
-                for (int q = 0; q < kLastRegs; q++) cl[q] = (q + 1 < us) ? S.C[lrow1 + q][lane()] : 0.0;
-#endif
                 // exact entries: a lane past the pool's end starts at +inf, so its values leave every
                 // running minimum alone (a dead path gives DOUBLE_MIN on every lane, valid or not)
                 // and the leaf loop below needs no per-lane condition -- no exec-mask switching
@@ -576,126 +509,18 @@ __global__ void __launch_bounds__(kLeafWaves * kWave, SGUFP_LEAF_MIN_WAVES) k_ex
                 const uint32_t open = uni(alive & ~done);
                 const uint32_t need = uni(nx ? alive : open);
                 double par = root;
-#if SGUFP_LEAF_FAST
-                if constexpr (!NX) {
-                    // exact entries: walks only for open leaves (a skipped leaf's walk is owed to the
-                    // next open one: it starts at the shallowest first-differing layer since the last
-                    // walk, `pend`), scalar-branch tests on the masks, the row read at a precomputed
-                    // offset.  The same adds in the same order as the general loop below.
-                    const LDS char *cbase = (const LDS char *)&S.C[0][lane()];
-                    int pend = T - 1;
-#if SGUFP_LEAF_FAST == 2
-                    // pairs of leaves: both coefficient reads are issued before either leaf's walk or
-                    // add (they do not depend on the parent's value), one LDS round trip per pair
-                    static_assert(kLeavesPerWave % 2 == 0, "leaf pairs");
-#pragma unroll
-                    for (int jp = 0; jp < kLeavesPerWave; jp += 2) {
-                        const uint32_t o2 = (open >> jp) & 3u;
-                        if (!o2 && !((walkm >> jp) & 3u)) continue;
-                        double c2[2] = {0.0, 0.0};
-#pragma unroll
-                        for (int q = 0; q < 2; q++)
-                            if (((o2 >> q) & 1u) && !((specm >> (jp + q)) & 1u))
-                                c2[q] = *(const LDS double *)(cbase + (uint32_t)__builtin_amdgcn_readlane((int)lpo, jp + q));
-#pragma unroll
-                        for (int q = 0; q < 2; q++) {
-                            const int j = jp + q;
-                            if ((o2 >> q) & 1u) {
-                                if (((walkm >> j) & 1u) || pend < T - 1) {
-                                    const int dj = j == 0 ? 1 : (int)((uint32_t)__builtin_amdgcn_readlane((int)lp, j) >> 8);
-                                    par = walk_down(S, w, j, min(pend, dj), T, us, root, ilo, ihi);
-                                    pend = T - 1;
-                                }
-                                double v;
-                                if ((specm >> j) & 1u)
-                                    v = ((uint32_t)__builtin_amdgcn_readlane((int)lp, j) & 0x7Fu) == kRowDead ? EDMIN : par;
-                                else
-                                    v = par + c2[q];
-                                m[j] = vmin64(m[j], v);
-                            } else if ((walkm >> j) & 1u) {
-                                const int dj = j == 0 ? 1 : (int)((uint32_t)__builtin_amdgcn_readlane((int)lp, j) >> 8);
-                                pend = min(pend, dj);
-                            }
-                        }
-                    }
-                    if (false)
-#endif
-#pragma unroll
-                    for (int j = 0; j < kLeavesPerWave; j++) {
-                        if ((open >> j) & 1u) {
-                            if (((walkm >> j) & 1u) || pend < T - 1) {
-                                const int dj = j == 0 ? 1 : (int)((uint32_t)__builtin_amdgcn_readlane((int)lp, j) >> 8);
-                                par = walk_down(S, w, j, min(pend, dj), T, us, root, ilo, ihi);
-                                pend = T - 1;
-                            }
-                            double v;
-                            if ((specm >> j) & 1u) {
-                                v = ((uint32_t)__builtin_amdgcn_readlane((int)lp, j) & 0x7Fu) == kRowDead ? EDMIN : par;
-                            } else {
-                                const uint32_t off = (uint32_t)__builtin_amdgcn_readlane((int)lpo, j);
-                                v = par + *(const LDS double *)(cbase + off);
-                            }
-                            m[j] = vmin64(m[j], v);
-                        } else if ((walkm >> j) & 1u) {
-                            const int dj = j == 0 ? 1 : (int)((uint32_t)__builtin_amdgcn_readlane((int)lp, j) >> 8);
-                            pend = min(pend, dj);
-                        }
-                    }
-                } else
-#endif
-                {
-#if SGUFP_LEAF_REGS
-                // ancestor values in registers (anc[k] = local layer k): a leaf recomputes the
-                // levels from its first ancestor that differs from the previous leaf's (dv), the
-                // same adds in the same order as walk_down, without its LDS round trip per level
-                double anc[kExactMaxT - 1];
-                anc[0] = root;
-#pragma unroll
-                for (int k = 1; k < kExactMaxT - 1; k++) anc[k] = root;
-#endif
 #pragma unroll
                 for (int j = 0; j < kLeavesPerWave; j++) {
                     if (j < cnt) {
                         const uint32_t x = (uint32_t)__builtin_amdgcn_readlane((int)lp, j);
                         const int dj = (int)(x >> 8);
-#if SGUFP_LEAF_REGS
-                        if (dj < T - 1 || j == 0) {
-#pragma unroll
-                            for (int k = 1; k < kExactMaxT - 1; k++) {
-                                if (k < T - 1 && k >= dj) {
-                                    const uint32_t bq = uni((uint32_t)S.lw[w].info[j][k]);
-                                    const uint32_t r = bq & 63u;
-                                    anc[k] = !(bq & 128u) ? EDMIN : (r ? anc[k - 1] + S.C[(k - 1) * us + r][lane()] : anc[k - 1]);
-                                }
-                            }
-                            par = anc[0];
-#pragma unroll
-                            for (int k = 1; k < kExactMaxT - 1; k++) par = (k == T - 2) ? anc[k] : par;
-                        }
-#else
                         if (dj < T - 1 || j == 0) par = walk_down(S, w, j, dj, T, us, root, ilo, ihi);
-#endif
                         if ((need >> j) & 1u) {
                             const uint32_t row = x & 0x7Fu;
                             double v;
                             if (row == kRowDead) v = EDMIN;
                             else if (row == kRowNoAdd) v = par;
-                            else {
-#if SGUFP_LEAF_LASTREG
-                                const uint32_t q = row - (uint32_t)lrow1;   // rank - 1 (wave-uniform)
-                                double c;
-                                if (q < (uint32_t)kLastRegs) {
-                                    c = cl[0];
-#pragma unroll
-                                    for (int qq = 1; qq < kLastRegs; qq++) c = (q == (uint32_t)qq) ? cl[qq] : c;
-                                } else {
-                                    c = S.C[row][lane()];
-                                }
-                                v = par + c;
-#else
-                                v = par + S.C[row][lane()];
-#endif
-                            }
+                            else v = par + S.C[row][lane()];
                             if (nx) {
                                 if (!ph2 && vc && ((open >> j) & 1u)) m[j] = rmin(m[j], v);
                             } else if ((open >> j) & 1u) {
@@ -716,7 +541,6 @@ __global__ void __launch_bounds__(kLeafWaves * kWave, SGUFP_LEAF_MIN_WAVES) k_ex
                             }
                         }
                     }
-                }
                 }
                 // every fourth block (and the last): leaves some lane already took to <= optimalLB
                 if (!nx && ((bb & 3) == 3 || bb == nlim - 1)) {
@@ -771,7 +595,7 @@ __global__ void __launch_bounds__(kLeafWaves * kWave, SGUFP_LEAF_MIN_WAVES) k_ex
             const int nbs_item = max(0, nb_done - bfrom);   // (phase B: bfrom = bsplit)
             atomicAdd(&ex.ctr[pb ? 19 : 3], (unsigned long long)max(0, nb_done - (pb ? bsplit : 0)));
             const uint64_t rm = (uint64_t)S.rmask[0] | (uint64_t)S.rmask[1] << 32;
-            atomicAdd(&ex.ctr[20], (unsigned long long)(SGUFP_LEAF_ROWMASK ? __popcll(rm) : E) * (unsigned long long)nbs_item);
+            atomicAdd(&ex.ctr[20], (unsigned long long)__popcll(rm) * (unsigned long long)nbs_item);
             atomicAdd(&ex.ctr[21], (unsigned long long)nbs_item);
         }
 #ifdef SGUFP_LEAF_CLOCKS
