@@ -2,16 +2,23 @@
 // DDSolver master/worker loop (DDSolver.cpp:556-846) around NodeExplorer::process
 // (NodeExplorer.cpp:915-986), with the open-node frontier resident in HBM.
 //
-// One round (sgufp_bnb_step) = what the reference's workers do for a batch of popped nodes:
-//   1. pop the top `b` records of the frontier stack (LIFO like lf_queue::pop);
-//   2. prune records with ub <= zOpt unprocessed (DDSolver.cpp:707-711) -- inside k_relax;
-//   3. process every other record against the current pools and zOpt (k_relax + k_emit);
-//   4. exact DDs run the refinement loop of NodeExplorer.cpp:946-969: argmax path, stop when
-//      the path was seen ({ub, ub}), else the device scenario subproblem, the new cut is
-//      appended to the global pool (Container::add) and applied to that DD (k_refine);
-//   5. incumbent = max(zOpt, lb of closed exact DDs)  (the CAS at DDSolver.cpp:723-731);
-//   6. cutset children of parents with ub > zOpt are pushed (DDSolver.cpp:744-748),
-//      compacted from the emit buffers onto the stack where the popped batch was.
+// One round (sgufp_bnb_step) = what the reference's workers do for a batch of popped nodes,
+// as the steps of BnbRound:
+//   pop_and_relax     pop the top `b` records of the frontier stack (LIFO like lf_queue::pop);
+//                     records with ub <= zOpt are pruned unprocessed (DDSolver.cpp:707-711) inside
+//                     k_relax, every other one is processed against the current pools and zOpt
+//                     (k_relax + k_emit);
+//   classify          the statuses: counters, and the exact DDs that enter their loop;
+//   refine            exact DDs run the refinement loop of NodeExplorer.cpp:946-969: argmax path,
+//                     stop when the path was seen ({ub, ub}), else the device scenario subproblem,
+//                     the new cut is appended to the global pool (Container::add) and applied to
+//                     that DD (k_refine); the round's limits cut loops short (deferred);
+//   save_deferred     the deferred records and their seen paths are kept on the host;
+//   update_incumbent  max(zOpt, lb of closed exact DDs)  (the CAS at DDSolver.cpp:723-731);
+//   push_children     cutset children of parents with ub > zOpt are pushed (DDSolver.cpp:744-748),
+//                     compacted from the emit buffers onto the stack where the popped batch was;
+//   push_deferred     the deferred records go back on top of the children, in their frontier
+//                     order and with the bound their loop reached: popped first next round.
 // Records processed in one round all see the same zOpt and pools, as concurrent workers
 // of the reference may.  Children of a parent keep the reference's cutset order; parents
 // keep their frontier order, so the top of the stack is the last parent's first child.
@@ -224,26 +231,51 @@ void sgufp_ctx::make_record_key(uint16_t gl, uint32_t mask, const int16_t *sol, 
     if (len) std::memcpy(&key[6], sol, 2 * len);
 }
 
-bool sgufp_ctx::slice_keys(int64_t lo, int count, std::vector<std::string> &keys) {
-    keys.assign((size_t)count, std::string());
-    if (count <= 0) return true;
-    std::vector<uint16_t> gl(count), len(count);
-    std::vector<uint32_t> mask(count);
-    std::vector<int64_t> so(count);
-    if (!download(gl.data(), fr.gl + lo, count) || !download(mask.data(), fr.mask + lo, count) ||
-        !download(len.data(), fr.sol_len + lo, count) || !download(so.data(), fr.sol_off + lo, count) || !sync())
+std::string FrontierRecords::key(int k) const {
+    std::string key;
+    sgufp_ctx::make_record_key(gl[k], mask[k], sol.data() + off[k], len[k], key);
+    return key;
+}
+
+void FrontierRecords::append(const FrontierRecords &r, int k) {
+    gl.push_back(r.gl[k]);
+    lb.push_back(r.lb[k]);
+    ub.push_back(r.ub[k]);
+    mask.push_back(r.mask[k]);
+    valid.push_back(r.valid[k]);
+    len.push_back(r.len[k]);
+    off.push_back((int64_t)sol.size());
+    sol.insert(sol.end(), r.sol.begin() + r.off[k], r.sol.begin() + r.off[k] + r.len[k]);
+}
+
+bool sgufp_ctx::read_frontier(int64_t lo, int n, FrontierRecords &r) {
+    r.gl.resize(n); r.lb.resize(n); r.ub.resize(n); r.mask.resize(n); r.valid.resize(n); r.len.resize(n);
+    // arena span of the entries: offsets increase with the entry index, up to the next entry's
+    // offset or, at the top of the stack, the top of the arena
+    const bool top = lo + n >= fr_n;
+    r.off.assign((size_t)n + 1, fr_sol_top);
+    if (!download(r.gl.data(), fr.gl + lo, n) || !download(r.lb.data(), fr.lb + lo, n) ||
+        !download(r.ub.data(), fr.ub + lo, n) || !download(r.mask.data(), fr.mask + lo, n) ||
+        !download(r.valid.data(), fr.valid + lo, n) || !download(r.len.data(), fr.sol_len + lo, n) ||
+        !download(r.off.data(), fr.sol_off + lo, (size_t)n + (top ? 0 : 1)) || !sync())
         return false;
-    // solution offsets grow with the entry index: one span covers the slice
-    int64_t s_lo = so[0], s_hi = so[0];
-    for (int k = 0; k < count; k++) {
-        s_lo = std::min(s_lo, so[k]);
-        s_hi = std::max(s_hi, so[k] + (int64_t)len[k]);
-    }
-    std::vector<int16_t> arena((size_t)(s_hi - s_lo));
-    if (!arena.empty() && (!download(arena.data(), fr.sol + s_lo, arena.size()) || !sync())) return false;
-    for (int k = 0; k < count; k++)
-        make_record_key(gl[k], mask[k], arena.data() + (so[k] - s_lo), len[k], keys[k]);
+    const int64_t s_lo = r.off[0];
+    r.sol.resize((size_t)(r.off[n] - s_lo));
+    if (!download(r.sol.data(), fr.sol + s_lo, r.sol.size()) || !sync()) return false;
+    r.off.pop_back();
+    for (auto &o : r.off) o -= s_lo;
     return true;
+}
+
+bool sgufp_ctx::write_frontier(int64_t e0, int64_t s0, const FrontierRecords &r) {
+    const size_t n = r.gl.size();
+    if (!frontier_reserve(e0 + (int64_t)n, (size_t)s0 + r.sol.size())) return false;
+    std::vector<int64_t> off(r.off);
+    for (auto &o : off) o += s0;
+    return upload(fr.gl + e0, r.gl.data(), n) && upload(fr.lb + e0, r.lb.data(), n) &&
+           upload(fr.ub + e0, r.ub.data(), n) && upload(fr.mask + e0, r.mask.data(), n) &&
+           upload(fr.valid + e0, r.valid.data(), n) && upload(fr.sol_len + e0, r.len.data(), n) &&
+           upload(fr.sol_off + e0, off.data(), n) && upload(fr.sol + s0, r.sol.data(), r.sol.size()) && sync();
 }
 
 int sgufp_frontier_clear(sgufp_ctx *ctx) {
@@ -274,58 +306,33 @@ int sgufp_frontier_push(sgufp_ctx *ctx, int n, const uint16_t *gl, const double 
                         const int64_t *states_off, const int16_t *states, const int64_t *sol_off, const int16_t *sol) {
     if (!ctx || n < 0 || (n && (!gl || !lb || !ub || !states_off || !sol_off))) return SGUFP_ERR_ARG;
     if (n == 0) return SGUFP_OK;
-    EncodedRecords e;
+    FrontierRecords e;
     ctx->encode_records(n, gl, states_off, states, sol_off, sol, e);
-    const int64_t base = ctx->fr_n;
-    const int64_t sbase = ctx->fr_sol_top;
-    if (!ctx->frontier_reserve(base + n, (size_t)sbase + e.sols.size())) return SGUFP_ERR_HIP;
-    for (auto &o : e.soff) o += sbase;
-    FrontierDev &f = ctx->fr;
-    if (!ctx->upload(f.gl + base, gl, n) || !ctx->upload(f.lb + base, lb, n) || !ctx->upload(f.ub + base, ub, n) ||
-        !ctx->upload(f.mask + base, e.mask.data(), n) || !ctx->upload(f.valid + base, e.valid.data(), n) ||
-        !ctx->upload(f.sol_off + base, e.soff.data(), n) || !ctx->upload(f.sol_len + base, e.slen.data(), n) ||
-        !ctx->upload(f.sol + sbase, e.sols.data(), e.sols.size()) || !ctx->sync())
-        return SGUFP_ERR_HIP;
+    e.gl.assign(gl, gl + n);
+    e.lb.assign(lb, lb + n);
+    e.ub.assign(ub, ub + n);
+    if (!ctx->write_frontier(ctx->fr_n, ctx->fr_sol_top, e)) return SGUFP_ERR_HIP;
     ctx->fr_n += n;
-    ctx->fr_sol_top += (int64_t)e.sols.size();
+    ctx->fr_sol_top += (int64_t)e.sol.size();
     return SGUFP_OK;
 }
 
-// host copies of the frontier entries [lo, lo + n): records (states decoded, solutions
-// re-based to 0) and, when keys is given, their deferred-loop keys
+// the frontier entries [lo, lo + n) for a caller: r, decoded to the caller's arrays (states,
+// solutions re-based to 0)
 static int read_records(sgufp_ctx *ctx, int64_t lo, int n, uint16_t *gl, double *lb, double *ub, int64_t *states_off,
-                        int16_t *states, int64_t *sol_off, int16_t *sol, std::vector<std::string> *keys) {
-    FrontierDev &f = ctx->fr;
-    std::vector<uint16_t> g(n), len(n);
-    std::vector<double> l(n), u(n);
-    std::vector<uint32_t> mask(n);
-    std::vector<int64_t> so(n + 1);
-    if (!ctx->download(g.data(), f.gl + lo, n) || !ctx->download(l.data(), f.lb + lo, n) ||
-        !ctx->download(u.data(), f.ub + lo, n) || !ctx->download(mask.data(), f.mask + lo, n) ||
-        !ctx->download(len.data(), f.sol_len + lo, n) || !ctx->download(so.data(), f.sol_off + lo, n) || !ctx->sync())
-        return SGUFP_ERR_HIP;
-    // arena span of the records (offsets increase with the entry index)
-    int64_t s_hi = ctx->fr_sol_top;
-    if (lo + n < ctx->fr_n && (!ctx->download(&s_hi, f.sol_off + lo + n, 1) || !ctx->sync())) return SGUFP_ERR_HIP;
-    const int64_t s_lo = so[0];
-    std::vector<int16_t> arena((size_t)(s_hi - s_lo));
-    if (!ctx->download(arena.data(), f.sol + s_lo, arena.size()) || !ctx->sync()) return SGUFP_ERR_HIP;
-    if (gl) std::copy(g.begin(), g.end(), gl);
-    if (lb) std::copy(l.begin(), l.end(), lb);
-    if (ub) std::copy(u.begin(), u.end(), ub);
-    ctx->decode_states(g.data(), mask.data(), (size_t)n, states_off, states);
+                        int16_t *states, int64_t *sol_off, int16_t *sol, FrontierRecords &r) {
+    if (!ctx->read_frontier(lo, n, r)) return SGUFP_ERR_HIP;
+    if (gl) std::copy(r.gl.begin(), r.gl.end(), gl);
+    if (lb) std::copy(r.lb.begin(), r.lb.end(), lb);
+    if (ub) std::copy(r.ub.begin(), r.ub.end(), ub);
+    ctx->decode_states(r.gl.data(), r.mask.data(), (size_t)n, states_off, states);
     int64_t o = 0;
     for (int k = 0; k < n; k++) {
         if (sol_off) sol_off[k] = o;
-        if (sol) std::memcpy(sol + o, arena.data() + (so[k] - s_lo), len[k] * sizeof(int16_t));
-        o += len[k];
+        if (sol) std::memcpy(sol + o, r.sol.data() + r.off[k], r.len[k] * sizeof(int16_t));
+        o += r.len[k];
     }
     if (sol_off) sol_off[n] = o;
-    if (keys) {
-        keys->assign((size_t)n, std::string());
-        for (int k = 0; k < n; k++)
-            sgufp_ctx::make_record_key(g[k], mask[k], arena.data() + (so[k] - s_lo), len[k], (*keys)[k]);
-    }
     return SGUFP_OK;
 }
 
@@ -358,12 +365,8 @@ int sgufp_frontier_peek_size(sgufp_ctx *ctx, int64_t first, int n, int64_t *n_st
 int sgufp_frontier_peek(sgufp_ctx *ctx, int64_t first, int n, uint16_t *gl, double *lb, double *ub,
                         int64_t *states_off, int16_t *states, int64_t *sol_off, int16_t *sol) {
     if (!ctx || n < 0 || first < 0 || first + n > ctx->fr_n) return SGUFP_ERR_ARG;
-    if (n == 0) {
-        if (states_off) states_off[0] = 0;
-        if (sol_off) sol_off[0] = 0;
-        return SGUFP_OK;
-    }
-    return read_records(ctx, first, n, gl, lb, ub, states_off, states, sol_off, sol, nullptr);
+    FrontierRecords r;
+    return read_records(ctx, first, n, gl, lb, ub, states_off, states, sol_off, sol, r);
 }
 
 int sgufp_frontier_take(sgufp_ctx *ctx, int n, int from_bottom, uint16_t *gl, double *lb, double *ub,
@@ -376,14 +379,13 @@ int sgufp_frontier_take(sgufp_ctx *ctx, int n, int from_bottom, uint16_t *gl, do
     }
     const int64_t total = ctx->fr_n;
     const int64_t lo = from_bottom ? 0 : total - n;
-    std::vector<std::string> keys;
-    const int rc = read_records(ctx, lo, n, gl, lb, ub, states_off, states, sol_off, sol,
-                                ctx->deferred_seen.empty() ? nullptr : &keys);
+    FrontierRecords r;
+    const int rc = read_records(ctx, lo, n, gl, lb, ub, states_off, states, sol_off, sol, r);
     if (rc != SGUFP_OK) return rc;
     // a taken record leaves this context (another shard, or the caller): its deferred loop's
     // seen list goes no further (the receiver restarts the loop; re-solving a path only
     // re-adds a valid cut)
-    for (auto &k : keys) ctx->deferred_seen.erase(k);
+    for (int k = 0; k < n && !ctx->deferred_seen.empty(); k++) ctx->deferred_seen.erase(r.key(k));
     if (!from_bottom || n == total) {
         int64_t s_lo = 0;
         if (!ctx->download(&s_lo, ctx->fr.sol_off + lo, 1) || !ctx->sync()) return SGUFP_ERR_HIP;
@@ -402,16 +404,9 @@ int sgufp_cuts_rows(sgufp_ctx *ctx, int is_feasibility, int first, int count, do
     if (count == 0) return SGUFP_OK;
     // one gather kernel ({rhs, row} blocks) and one download instead of a copy per row
     const size_t stride = (size_t)ctx->net.n_slots + 1, blk = stride + 1;
-    if ((size_t)count * blk > ctx->rowbuf_cap) {
-        if (ctx->d_rowbuf) ctx->release(ctx->d_rowbuf);
-        ctx->rowbuf_cap = std::max((size_t)count * blk, 2 * ctx->rowbuf_cap);
-        if (!ctx->alloc(ctx->d_rowbuf, ctx->rowbuf_cap, "cut rows")) return SGUFP_ERR_HIP;
-    }
-    if ((size_t)count > ctx->rowids_cap) {
-        if (ctx->d_rowids) ctx->release(ctx->d_rowids);
-        ctx->rowids_cap = std::max((size_t)count, 2 * ctx->rowids_cap);
-        if (!ctx->alloc(ctx->d_rowids, ctx->rowids_cap, "cut rows")) return SGUFP_ERR_HIP;
-    }
+    if (!ctx->grow(ctx->d_rowbuf, ctx->rowbuf_cap, (size_t)count * blk, "cut rows") ||
+        !ctx->grow(ctx->d_rowids, ctx->rowids_cap, (size_t)count, "cut rows"))
+        return SGUFP_ERR_HIP;
     std::vector<double> buf((size_t)count * blk);
     if (!ctx->upload(ctx->d_rowids, v.data() + first, (size_t)count) ||
         !ctx->hip_ok(launch_gather_rows(ctx->d_rows, ctx->d_rhs, ctx->d_rowids, count, (int)stride, ctx->d_rowbuf,
@@ -425,199 +420,167 @@ int sgufp_cuts_rows(sgufp_ctx *ctx, int is_feasibility, int first, int count, do
     return SGUFP_OK;
 }
 
-int sgufp_bnb_step(sgufp_ctx *ctx, int max_nodes, double *incumbent, sgufp_bnb_stats *stats) {
-    if (!ctx || !incumbent) return SGUFP_ERR_ARG;
+}  // extern "C"
+
+namespace {
+
+// One round of sgufp_bnb_step: the steps of the header comment as methods, in the order they
+// run, over the host state of the round.  Every step returns an SGUFP_* code.
+struct BnbRound {
+    sgufp_ctx &c;
+    double &incumbent;           // in: the round's zOpt; out: update_incumbent
+    const double z;
+    const int b;                 // popped records (batch slots 0 .. b-1)
+    const int64_t base;          // their first frontier entry
+    const std::chrono::steady_clock::time_point t_round = std::chrono::steady_clock::now();
+    BatchOut &o;
     sgufp_bnb_stats S{};
-    const auto t_round = std::chrono::steady_clock::now();
-    const double z = *incumbent;
-    const int64_t T = ctx->fr_n;
-    if (T == 0) {
-        if (stats) *stats = S;
-        return SGUFP_OK;
-    }
-    int b = ctx->max_batch;
-    if (max_nodes > 0) b = std::min(b, max_nodes);
-    b = (int)std::min<int64_t>(b, T);
-    const int64_t base = T - b;
-    S.popped = b;
 
-    for (auto &t : ctx->trace_items) t.clear();
-    // deferred loops: keys of the popped records (resumed below, or dropped when pruned)
-    std::vector<std::string> keys;
-    if (!ctx->deferred_seen.empty() && !ctx->slice_keys(base, b, keys)) return SGUFP_ERR_HIP;
-    std::vector<double> ub_in;
-    if (ctx->trace) {
-        ub_in.resize(b);
-        if (!ctx->download(ub_in.data(), ctx->fr.ub + base, b) || !ctx->sync()) return SGUFP_ERR_HIP;
+    // per batch slot
+    std::vector<int32_t> st;
+    std::vector<double> ub, lbv;
+    std::vector<uint32_t> nch, need, dn, da, sw;
+    std::vector<int32_t> nseen;                  // paths on the slot's seen list
+    int64_t sol_start = 0;                       // arena position of the popped slice
+    // host copy of the popped slice: read before the relaxation when deferred loops exist (their
+    // keys) or the round is traced, else by save_deferred when it has records to save
+    FrontierRecords popped;
+    std::vector<std::string> keys;               // per slot, when deferred loops exist
+    std::vector<int> exact, closed, deferred;    // slots that entered their loop / closed it / were cut short
+    std::vector<std::vector<std::vector<int16_t>>> seen_host;   // the deferred records' seen lists
+    FrontierRecords kept;                        // the deferred records (save_deferred -> push_deferred)
+    double znew = 0.0;
+
+    // refinement loop: k_loop_check's answers for the records still in their loop, and the fresh
+    // records of the previous iteration, whose cuts (pool rows prev_first ...) file_rows files
+    std::vector<int32_t> flag, chains, ptype;
+    std::vector<int> prev;
+    int prev_first = 0;
+    std::vector<double> pub, pobj;               // their rows' bounds; trace: their sum_s obj_s / S
+    std::vector<size_t> prev_trace;              // trace: their items of kind 1
+    std::vector<uint16_t> tlen;                  // trace: the argmax paths the loop check saw
+    std::vector<int16_t> tpath;
+
+    BnbRound(sgufp_ctx &ctx, double &inc, int n)
+        : c{ctx}, incumbent{inc}, z{inc}, b{n}, base{ctx.fr_n - n}, o{ctx.out} {
+        S.popped = b;
     }
 
-    // 1-3: relax the top of the stack in place
-    ctx->n = b;
-    ctx->cur = ctx->frontier_slice(base, b);
-    ctx->restricted_done = false;
-    if (!ctx->relax_current(z)) return SGUFP_ERR_HIP;
-    std::vector<int32_t> st(b);
-    std::vector<double> ub(b), lbv(b, -__DBL_MAX__);
-    std::vector<uint32_t> nch(b), need(b), dn(b), da(b), sw(b);
-    std::vector<uint64_t> coff(b + 1), soff(b + 1);
-    int64_t sol_start = 0;
-    BatchOut &o = ctx->out;
-    if (!ctx->download(st.data(), o.status, b) || !ctx->download(ub.data(), o.ub, b) ||
-        !ctx->download(nch.data(), o.nchild, b) || !ctx->download(need.data(), o.sol_need, b) ||
-        !ctx->download(coff.data(), ctx->d_coff, b + 1) || !ctx->download(soff.data(), ctx->d_soff, b + 1) ||
-        !ctx->download(dn.data(), o.dd_nodes, b) || !ctx->download(da.data(), o.dd_arcs, b) ||
-        !ctx->download(sw.data(), o.sweeps, b) || !ctx->download(&sol_start, ctx->fr.sol_off + base, 1) ||
-        !ctx->sync())
-        return SGUFP_ERR_HIP;
-    if (ctx->timing) hipEventElapsedTime(&ctx->ms_relax, ctx->ev[0], ctx->ev[1]);
-    S.ms_relax = ctx->timing ? ctx->ms_relax : 0.0;
-    std::vector<int> act, closed;
-    for (int k = 0; k < b; k++) {
-        switch (st[k]) {
-            case SGUFP_PRUNED_BY_BOUND: S.pruned_bound++; continue;
-            case SGUFP_PRUNED_BY_FEASIBILITY_CUT: S.pruned_feasibility++; break;
-            case SGUFP_PRUNED_BY_OPTIMALITY_CUT: S.pruned_optimality++; break;
-            case SGUFP_NEEDS_SUBPROBLEM: act.push_back(k); break;
-            case SGUFP_SUCCESS: break;
-            default: {
-                char msg[128];
-                std::snprintf(msg, sizeof msg, "B&B round: frontier record %lld failed with node status %d",
-                              (long long)(base + k), st[k]);
-                ctx->err = msg;
-                return SGUFP_ERR_STATE;
-            }
-        }
-        S.relaxed++;
-        S.children += nch[k];
-        S.dd_nodes += dn[k];
-        S.dd_arcs += da[k];
-        S.sweeps += sw[k];
-    }
-    S.exact = (int64_t)act.size();
-    if (ctx->trace) {
+    // ---- trace (sgufp_bnb_set_trace): kinds 0 popped, 1 subproblems, 2 closed loops, 3 waves ----
+    int trace_popped() {
         std::vector<uint64_t> ticks(b);
         std::vector<uint32_t> redo(b);
-        if (!ctx->download(ticks.data(), o.ticks, b) || !ctx->download(redo.data(), o.redo, b) || !ctx->sync())
+        if (!c.download(ticks.data(), o.ticks, b) || !c.download(redo.data(), o.redo, b) || !c.sync())
             return SGUFP_ERR_HIP;
         const bool stamped = relax_has_phases();
         for (int k = 0; k < b; k++) {
-            ctx->trace_items[0].emplace_back();
-            auto &t = ctx->trace_items[0].back();
-            t.record = k;
-            t.code = st[k];
-            t.value = ub_in[k];
-            ctx->trace_items[3].emplace_back();
-            auto &u = ctx->trace_items[3].back();
-            u.record = k;
-            u.code = (int32_t)(redo[k] & 0xFF);
-            u.row = (int32_t)sw[k];
-            u.value = stamped ? (double)ticks[k] : 0.0;
+            c.trace_items[0].push_back({k, st[k], -1, popped.ub[k], {}});
+            c.trace_items[3].push_back({k, (int32_t)(redo[k] & 0xFF), (int32_t)sw[k], stamped ? (double)ticks[k] : 0.0, {}});
+        }
+        return SGUFP_OK;
+    }
+    bool trace_paths() {   // the argmax paths as the loop check saw them
+        tlen.resize((size_t)b);
+        tpath.resize((size_t)b * c.sc.Lcap);
+        return c.download(tlen.data(), o.path_len, (size_t)b) && c.download(tpath.data(), o.path, tpath.size()) &&
+               c.sync();
+    }
+    std::vector<int16_t> slot_path(int k) const {
+        const size_t Lc = (size_t)c.sc.Lcap;
+        return std::vector<int16_t>(tpath.begin() + (long)(k * Lc), tpath.begin() + (long)(k * Lc + tlen[k]));
+    }
+    void trace_closed(int k) {
+        c.trace_items[2].push_back({k, 0, -1, 0.0, slot_path(k)});   // value: the bound after the loop
+    }
+    void trace_subproblems(const std::vector<int> &fresh) {
+        prev_trace.clear();
+        for (int k : fresh) {
+            prev_trace.push_back(c.trace_items[1].size());
+            c.trace_items[1].push_back({k, -1, -1, 0.0, slot_path(k)});   // code, row, value: file_rows
         }
     }
-    // a popped record that left its deferred loop without re-entering it (pruned by bound
-    // or by a cut of the grown pool) drops its seen list
-    if (!keys.empty())
-        for (int k = 0; k < b; k++)
-            if (st[k] != SGUFP_NEEDS_SUBPROBLEM) ctx->deferred_seen.erase(keys[k]);
 
-    // 4: refinement loop of the exact DDs (NodeExplorer.cpp:946-969), device-resident: per
-    // iteration k_loop_check (argmax path seen? -> {ub, ub}; else fresh), one synchronisation,
-    // then k_seen_append, the scenario subproblem on the fresh paths read in place,
-    // k_append_cuts (Container::add on the device) and k_refine, back to back on the stream.
-    // The host files the appended rows under the F / O lists at the next synchronisation.
-    // The loop of one record is a chain of dependent subproblems (one new cut per iteration);
-    // a round stops it after ctx->bnb_max_iters iterations or ctx->bnb_seconds, and the
-    // records still in their loop go back on top of the frontier (deferred) with the paths
-    // they have seen.  Popped again, such a record rebuilds its DD, applies the pool (its own
-    // new cuts included, so its bound is where the loop left it) and resumes the loop with
-    // that seen list: it ends exactly where the uninterrupted loop would (a path repeats).
-    std::vector<int> deferred;
-    std::vector<std::vector<std::vector<int16_t>>> seen_host;   // deferred records' lists
-    const int stride = ctx->net.n_slots + 1;
-    if (!act.empty()) {
-        if (!ctx->loop_reserve(b, 64)) return SGUFP_ERR_HIP;
-        std::vector<int32_t> nseen(b, 0);
-        if (!ctx->hip_ok(hipMemsetAsync(ctx->seen.n, 0, (size_t)b * 4, ctx->stream), "memset")) return SGUFP_ERR_HIP;
-        if (!keys.empty()) {
-            for (int k : act) {
-                auto it = ctx->deferred_seen.find(keys[k]);
-                if (it == ctx->deferred_seen.end()) continue;
-                const int cnt = (int)it->second.size();
-                if (!ctx->loop_reserve(b, cnt + 1)) return SGUFP_ERR_HIP;
-                if (!ctx->seen_upload(k, it->second)) return SGUFP_ERR_HIP;
-                nseen[k] = cnt;
-                ctx->deferred_seen.erase(it);
-                S.resumed++;
+    // ---- 1: pop the top b records and relax them in place (k_relax prunes by bound) ----
+    int pop_and_relax() {
+        for (auto &t : c.trace_items) t.clear();
+        if ((!c.deferred_seen.empty() || c.trace) && !c.read_frontier(base, b, popped)) return SGUFP_ERR_HIP;
+        if (!c.deferred_seen.empty())
+            for (int k = 0; k < b; k++) keys.push_back(popped.key(k));
+        c.n = b;
+        c.cur = c.frontier_slice(base, b);
+        c.restricted_done = false;
+        if (!c.relax_current(z)) return SGUFP_ERR_HIP;
+        st.resize(b); ub.resize(b); nch.resize(b); need.resize(b); dn.resize(b); da.resize(b); sw.resize(b);
+        lbv.assign(b, -__DBL_MAX__);
+        if (!c.download(st.data(), o.status, b) || !c.download(ub.data(), o.ub, b) ||
+            !c.download(nch.data(), o.nchild, b) || !c.download(need.data(), o.sol_need, b) ||
+            !c.download(dn.data(), o.dd_nodes, b) || !c.download(da.data(), o.dd_arcs, b) ||
+            !c.download(sw.data(), o.sweeps, b) || !c.download(&sol_start, c.fr.sol_off + base, 1) || !c.sync())
+            return SGUFP_ERR_HIP;
+        if (c.timing) hipEventElapsedTime(&c.ms_relax, c.ev[0], c.ev[1]);
+        S.ms_relax = c.timing ? c.ms_relax : 0.0;
+        return SGUFP_OK;
+    }
+
+    // ---- 2: the statuses: counters, the records that enter the refinement loop ----
+    int classify() {
+        for (int k = 0; k < b; k++) {
+            switch (st[k]) {
+                case SGUFP_PRUNED_BY_BOUND: S.pruned_bound++; continue;
+                case SGUFP_PRUNED_BY_FEASIBILITY_CUT: S.pruned_feasibility++; break;
+                case SGUFP_PRUNED_BY_OPTIMALITY_CUT: S.pruned_optimality++; break;
+                case SGUFP_NEEDS_SUBPROBLEM: exact.push_back(k); break;
+                case SGUFP_SUCCESS: break;
+                default: {
+                    char msg[128];
+                    std::snprintf(msg, sizeof msg, "B&B round: frontier record %lld failed with node status %d",
+                                  (long long)(base + k), st[k]);
+                    c.err = msg;
+                    return SGUFP_ERR_STATE;
+                }
             }
+            S.relaxed++;
+            S.children += nch[k];
+            S.dd_nodes += dn[k];
+            S.dd_arcs += da[k];
+            S.sweeps += sw[k];
         }
-        int na = (int)act.size();
-        if (!ctx->upload(ctx->d_lact, act.data(), (size_t)na)) return SGUFP_ERR_HIP;
-        std::vector<int32_t> flag, chains, ptype;
-        std::vector<double> pub;
-        std::vector<int> prev;            // fresh records of the previous iteration (rows filed below)
-        int prev_first = 0;
-        std::vector<double> pobj;         // trace: the previous iteration's sum_s obj_s / S
-        std::vector<size_t> prev_trace;   // trace: items of the previous iteration's subproblems
-        auto file_rows = [&]() -> bool {  // Container::add: feasibility list, optimality list
-            for (size_t i = 0; i < prev.size(); i++) {
-                if (ptype[i] < 0) {
-                    // the rows of that launch leave the pool again (they were appended and
-                    // applied on the device before the host saw the type); the batch's results
-                    // are not used past the error
-                    ctx->n_rows = prev_first;
-                    ctx->err = "scenario subproblem failed (invalid path or numerical failure)";
-                    return false;
-                }
-            }
-            ctx->row_ub.resize((size_t)ctx->n_rows);
-            for (int want = 1; want >= 0; want--)
-                for (size_t i = 0; i < prev.size(); i++) {
-                    if (ptype[i] != want) continue;
-                    auto &list = want ? ctx->f_rows : ctx->o_rows;
-                    if (ctx->trace) {
-                        auto &t = ctx->trace_items[1][prev_trace[i]];
-                        t.code = want;
-                        t.row = (int32_t)list.size();
-                        t.value = pobj[i];
-                    }
-                    list.push_back(prev_first + (int)i);
-                    ctx->row_ub[(size_t)prev_first + i] = pub[i];
-                    (want ? S.new_feasibility_cuts : S.new_optimality_cuts)++;
-                }
-            ctx->order_dirty = true;
-            prev.clear();
-            return true;
-        };
-        // trace: the argmax path of batch slot k as the loop check saw it
-        std::vector<uint16_t> tlen;
-        std::vector<int16_t> tpath;
-        const size_t Lc = (size_t)ctx->sc.Lcap;
-        auto slot_path = [&](int k) {
-            return std::vector<int16_t>(tpath.begin() + (long)(k * Lc), tpath.begin() + (long)(k * Lc + tlen[k]));
-        };
-        while (na > 0) {
-            if (!ctx->hip_ok(launch_loop_check(o, ctx->seen, ctx->d_lact, na, ctx->net.m, ctx->d_lflag, ctx->d_lchain,
-                                               ctx->stream), "k_loop_check"))
+        S.exact = (int64_t)exact.size();
+        if (c.trace && trace_popped() != SGUFP_OK) return SGUFP_ERR_HIP;
+        // a popped record that left its deferred loop without re-entering it (pruned by bound
+        // or by a cut of the grown pool) drops its seen list
+        if (!keys.empty())
+            for (int k = 0; k < b; k++)
+                if (st[k] != SGUFP_NEEDS_SUBPROBLEM) c.deferred_seen.erase(keys[k]);
+        return SGUFP_OK;
+    }
+
+    // ---- 3: the refinement loop of the exact DDs, device-resident: per iteration k_loop_check
+    // (argmax path seen? -> {ub, ub}; else fresh), one synchronisation, then k_seen_append, the
+    // scenario subproblem on the fresh paths read in place, k_append_cuts (Container::add on the
+    // device) and k_refine, back to back on the stream.  The host files the appended rows under
+    // the F / O lists at the next synchronisation.  The loop of one record is a chain of
+    // dependent subproblems (one new cut per iteration); a round stops it after bnb_max_iters
+    // iterations or bnb_seconds.  A record deferred so rebuilds its DD when popped again, applies
+    // the pool (its own new cuts included, so its bound is where the loop left it) and resumes
+    // with its seen list: it ends exactly where the uninterrupted loop would (a path repeats). ----
+    int refine() {
+        if (exact.empty()) return SGUFP_OK;
+        int rc = resume_loops();
+        if (rc != SGUFP_OK) return rc;
+        std::vector<int> act = exact;   // the records still in their loop, as in d_lact
+        if (!c.upload(c.d_lact, act.data(), act.size())) return SGUFP_ERR_HIP;
+        while (!act.empty()) {
+            const int na = (int)act.size();
+            if (!c.hip_ok(launch_loop_check(o, c.seen, c.d_lact, na, c.net.m, c.d_lflag, c.d_lchain, c.stream),
+                          "k_loop_check"))
                 return SGUFP_ERR_HIP;
             flag.resize(na);
             chains.resize(na);
-            ptype.resize(prev.size());
-            pub.resize(prev.size());
-            pobj.resize(prev.size());
-            if (!ctx->download(flag.data(), ctx->d_lflag, (size_t)na) ||
-                !ctx->download(chains.data(), ctx->d_lchain, (size_t)na) ||
-                !ctx->download(ptype.data(), ctx->sio.cut_type, prev.size()) ||
-                !ctx->download(pub.data(), ctx->d_lrowub, prev.size()) ||
-                (ctx->trace && !ctx->download(pobj.data(), ctx->sio.obj_mean, prev.size())) || !ctx->sync())   // the one sync
+            if (!c.download(flag.data(), c.d_lflag, (size_t)na) || !c.download(chains.data(), c.d_lchain, (size_t)na))
                 return SGUFP_ERR_HIP;
-            if (!file_rows()) return SGUFP_ERR_STATE;
-            if (ctx->trace) {
-                tlen.resize((size_t)b);
-                tpath.resize((size_t)b * Lc);
-                if (!ctx->download(tlen.data(), o.path_len, (size_t)b) || !ctx->download(tpath.data(), o.path, tpath.size()) ||
-                    !ctx->sync())
-                    return SGUFP_ERR_HIP;
-            }
+            if ((rc = file_rows()) != SGUFP_OK) return rc;   // the one sync
+            if (c.trace && !trace_paths()) return SGUFP_ERR_HIP;
             std::vector<int> fresh;
             int nct = 1;
             for (int a = 0; a < na; a++) {
@@ -625,11 +588,7 @@ int sgufp_bnb_step(sgufp_ctx *ctx, int max_nodes, double *incumbent, sgufp_bnb_s
                 if (flag[a] == 1) {                 // {ub, ub, {}, SUCCESS}
                     closed.push_back(k);
                     S.exact_closed++;
-                    if (ctx->trace) {
-                        ctx->trace_items[2].emplace_back();
-                        ctx->trace_items[2].back().record = k;
-                        ctx->trace_items[2].back().path = slot_path(k);
-                    }
+                    if (c.trace) trace_closed(k);
                 } else if (flag[a] == 2) {
                     fresh.push_back(k);
                     nct = std::max(nct, chains[a]);
@@ -640,208 +599,243 @@ int sgufp_bnb_step(sgufp_ctx *ctx, int max_nodes, double *incumbent, sgufp_bnb_s
                 }
             }
             if (fresh.empty()) break;
-            if ((ctx->bnb_max_iters > 0 && S.refine_iters >= ctx->bnb_max_iters) ||
-                (ctx->bnb_seconds > 0 && S.refine_iters > 0 && seconds_since(t_round) >= ctx->bnb_seconds)) {
+            if ((c.bnb_max_iters > 0 && S.refine_iters >= c.bnb_max_iters) ||
+                (c.bnb_seconds > 0 && S.refine_iters > 0 && seconds_since(t_round) >= c.bnb_seconds)) {
                 // (every round runs at least one iteration: a batch whose relaxation alone
                 // outlasts round_seconds still makes progress)
                 deferred.swap(fresh);    // their current path is unseen: solved when resumed
                 break;
             }
-            // With a round deadline, one iteration solves at most chunk_lps scenario LPs
-            // (a 1024-leaf iteration of the 512-scenario C5 network would take minutes); the
-            // other fresh records stay in the loop unchanged (path not yet seen) for the next
-            // iteration, or are deferred at the deadline.
             std::vector<int> rest;
-            if (ctx->bnb_seconds > 0) {
-                const size_t chunk = (size_t)std::max<int64_t>(1, ctx->chunk_lps / std::max(1, ctx->net.S));
-                if (fresh.size() > chunk) {
-                    rest.assign(fresh.begin() + (long)chunk, fresh.end());
-                    fresh.resize(chunk);
-                    nct = 1;
-                    for (int a = 0; a < na; a++)
-                        if (flag[a] == 2 && std::find(fresh.begin(), fresh.end(), act[a]) != fresh.end())
-                            nct = std::max(nct, chains[a]);
-                }
-            }
+            if (c.bnb_seconds > 0) rest = split_chunk(fresh, nct);
             S.refine_iters++;
             const int nf = (int)fresh.size();
             int most = 0;
             for (int k : fresh) most = std::max(most, ++nseen[k]);
-            if (!ctx->loop_reserve(b, most) || !ctx->upload(ctx->d_lact, fresh.data(), (size_t)nf) ||
-                !ctx->hip_ok(launch_seen_append(o, ctx->seen, ctx->d_lact, nf, ctx->net.m, ctx->stream), "k_seen_append") ||
-                !ctx->sub_init() || !ctx->sub_grow(nf, 1) || !ctx->grow_rows(ctx->n_rows + nf))
+            if (!c.loop_reserve(b, most) || !c.upload(c.d_lact, fresh.data(), (size_t)nf) ||
+                !c.hip_ok(launch_seen_append(o, c.seen, c.d_lact, nf, c.net.m, c.stream), "k_seen_append") ||
+                !c.sub_init() || !c.sub_grow(nf, 1) || !c.grow_rows(c.n_rows + nf))
                 return SGUFP_ERR_HIP;
-            SubIO io = ctx->sio;
-            io.n_paths = nf;
-            io.nct_cap = nct;
-            io.path_slot = ctx->d_lact;
-            io.path_len = o.path_len;
-            io.path_stride = ctx->sc.Lcap;
-            io.paths = o.path;
-            io.path_off = nullptr;
-            // warm starts: every path starts from the stored state of the closest path solved
-            // before (the record's own previous path, a sibling's, ...) and leaves its own state
-            // in the ring for the next ones (k_warm_pick, k_sub_scenario<..., WARM>)
-            if (ctx->warm_reserve()) {
-                if (!ctx->hip_ok(launch_warm_pick(io, ctx->wring, ctx->warm_ptr, ctx->stream), "k_warm_pick"))
-                    return SGUFP_ERR_HIP;
-                io.warm_src = ctx->wring.src;
-                io.warm_dst = ctx->wring.dst;
-                io.wst_x = ctx->d_wx;
-                io.wst_a = ctx->d_wa;
-                io.wst_ok = ctx->d_wok;
-                ctx->warm_ptr = (ctx->warm_ptr + nf) % ctx->wring.R;
-            }
-            if (!ctx->hip_ok(launch_subproblem(ctx->sn, io, ctx->stream), "subproblem launch")) return SGUFP_ERR_HIP;
-            ctx->sub_last_n = nf;
-            if (ctx->sub_stats) ctx->sub_stats_add(nf);
-            const int first = ctx->n_rows;
-            if (!ctx->hip_ok(launch_append_cuts(io.cut_type, io.cut_rhs, io.cut_row, nf, stride, first, ctx->d_rows,
-                                                ctx->d_rhs, ctx->d_coefT, ctx->nd.slot_tab, ctx->net.L, ctx->ustride,
-                                                ctx->d_lrowub, ctx->d_rcuts, ctx->d_rfeas, ctx->stream),
-                             "k_append_cuts") ||
-                !ctx->hip_ok(launch_refine(ctx->nd, ctx->sc, ctx->batch(), ctx->pool(), o, ctx->d_lact, ctx->d_rcuts,
-                                           ctx->d_rfeas, nf, z, ctx->ex, ctx->stream), "k_refine"))
+            SubIO io;
+            if (!sub_io(nf, nct, io) || !c.hip_ok(launch_subproblem(c.sn, io, c.stream), "subproblem launch"))
                 return SGUFP_ERR_HIP;
-            ctx->n_rows += nf;
+            c.sub_last_n = nf;
+            if (c.sub_stats) c.sub_stats_add(nf);
+            const int first = c.n_rows;
+            if (!c.hip_ok(launch_append_cuts(io.cut_type, io.cut_rhs, io.cut_row, nf, c.net.n_slots + 1, first, c.d_rows,
+                                             c.d_rhs, c.d_coefT, c.nd.slot_tab, c.net.L, c.ustride, c.d_lrowub, c.d_rcuts,
+                                             c.d_rfeas, c.stream), "k_append_cuts") ||
+                !c.hip_ok(launch_refine(c.nd, c.sc, c.batch(), c.pool(), o, c.d_lact, c.d_rcuts, c.d_rfeas, nf, z, c.ex,
+                                        c.stream), "k_refine"))
+                return SGUFP_ERR_HIP;
+            c.n_rows += nf;
             S.subproblems += nf;
             prev = fresh;
             prev_first = first;
-            if (ctx->trace) {
-                prev_trace.clear();
-                for (int i = 0; i < nf; i++) {
-                    prev_trace.push_back(ctx->trace_items[1].size());
-                    ctx->trace_items[1].emplace_back();
-                    auto &t = ctx->trace_items[1].back();
-                    t.record = fresh[i];
-                    t.code = -1;
-                    t.path = slot_path(fresh[i]);
-                }
-            }
+            if (c.trace) trace_subproblems(fresh);
             act = fresh;
             act.insert(act.end(), rest.begin(), rest.end());
-            na = (int)act.size();
-            if (!rest.empty() && !ctx->upload(ctx->d_lact + nf, rest.data(), rest.size())) return SGUFP_ERR_HIP;
+            if (!c.upload(c.d_lact + nf, rest.data(), rest.size())) return SGUFP_ERR_HIP;
         }
-        if (!prev.empty()) {
-            ptype.resize(prev.size());
-            pub.resize(prev.size());
-            pobj.resize(prev.size());
-            if (!ctx->download(ptype.data(), ctx->sio.cut_type, prev.size()) ||
-                !ctx->download(pub.data(), ctx->d_lrowub, prev.size()) ||
-                (ctx->trace && !ctx->download(pobj.data(), ctx->sio.obj_mean, prev.size())) || !ctx->sync())
-                return SGUFP_ERR_HIP;
-            if (!file_rows()) return SGUFP_ERR_STATE;
-        }
+        if (!prev.empty() && (rc = file_rows()) != SGUFP_OK) return rc;
         // bounds after the loop: closed records' lb (the incumbent candidates) and the
         // deferred records' bound
-        if (!ctx->download(ub.data(), o.ub, b) || !ctx->sync()) return SGUFP_ERR_HIP;
+        if (!c.download(ub.data(), o.ub, b) || !c.sync()) return SGUFP_ERR_HIP;
         for (int k : closed) lbv[k] = ub[k];
-        for (auto &t : ctx->trace_items[2]) t.value = ub[t.record];
+        for (auto &t : c.trace_items[2]) t.value = ub[t.record];
         for (int k : deferred) {
             seen_host.emplace_back();
-            if (!ctx->seen_download(k, nseen[k], seen_host.back())) return SGUFP_ERR_HIP;
+            if (!c.seen_download(k, nseen[k], seen_host.back())) return SGUFP_ERR_HIP;
         }
+        return SGUFP_OK;
     }
 
-    // deferred records: saved before the children overwrite the popped slice
-    const int nd = (int)deferred.size();
-    std::vector<uint16_t> d_gl(nd), d_len(nd);
-    std::vector<double> d_lb(nd), d_ub(nd);
-    std::vector<uint32_t> d_mask(nd);
-    std::vector<uint8_t> d_valid(nd);
-    std::vector<int64_t> d_soff(nd);
-    std::vector<std::vector<int16_t>> d_sol(nd);
-    {
-        FrontierDev &f = ctx->fr;
-        for (int i = 0; i < nd; i++) {
-            const int64_t e = base + deferred[i];
-            if (!ctx->download(&d_gl[i], f.gl + e, 1) || !ctx->download(&d_lb[i], f.lb + e, 1) ||
-                !ctx->download(&d_mask[i], f.mask + e, 1) || !ctx->download(&d_valid[i], f.valid + e, 1) ||
-                !ctx->download(&d_len[i], f.sol_len + e, 1) || !ctx->download(&d_soff[i], f.sol_off + e, 1))
-                return SGUFP_ERR_HIP;
-            d_ub[i] = ub[deferred[i]];   // the bound the loop reached (every pool cut is valid)
+    // empty seen lists for the batch slots; a record whose loop an earlier round deferred gets
+    // its list back
+    int resume_loops() {
+        if (!c.loop_reserve(b, 64)) return SGUFP_ERR_HIP;
+        nseen.assign(b, 0);
+        if (!c.hip_ok(hipMemsetAsync(c.seen.n, 0, (size_t)b * 4, c.stream), "memset")) return SGUFP_ERR_HIP;
+        if (keys.empty()) return SGUFP_OK;
+        for (int k : exact) {
+            auto it = c.deferred_seen.find(keys[k]);
+            if (it == c.deferred_seen.end()) continue;
+            const int cnt = (int)it->second.size();
+            if (!c.loop_reserve(b, cnt + 1) || !c.seen_upload(k, it->second)) return SGUFP_ERR_HIP;
+            nseen[k] = cnt;
+            c.deferred_seen.erase(it);
+            S.resumed++;
         }
-        if (nd && !ctx->sync()) return SGUFP_ERR_HIP;
-        for (int i = 0; i < nd; i++) {
-            d_sol[i].resize(d_len[i]);
-            if (!ctx->download(d_sol[i].data(), f.sol + d_soff[i], d_len[i])) return SGUFP_ERR_HIP;
-        }
-        if (nd && !ctx->sync()) return SGUFP_ERR_HIP;
-        for (int i = 0; i < nd; i++) {
-            std::string key;
-            sgufp_ctx::make_record_key(d_gl[i], d_mask[i], d_sol[i].data(), d_len[i], key);
-            ctx->deferred_seen[key] = std::move(seen_host[i]);
-        }
+        return SGUFP_OK;
     }
-    S.deferred = nd;
 
-    // 5: incumbent (DDSolver.cpp:723-731)
-    double znew = z;
-    for (int k = 0; k < b; k++)
-        if (lbv[k] > znew) znew = lbv[k];
-    S.improved = znew > z ? 1 : 0;
-    *incumbent = znew;
-
-    // 6: push the children of parents with ub > zOpt (DDSolver.cpp:744-748)
-    std::vector<int32_t> par;
-    std::vector<int64_t> dchild, dsol;
-    int64_t nc = 0, ns = 0;
-    for (int k = 0; k < b; k++) {
-        if (st[k] != SGUFP_SUCCESS || nch[k] == 0 || !(ub[k] > znew)) continue;
-        par.push_back(k);
-        dchild.push_back(base + nc);
-        dsol.push_back(sol_start + ns);
-        nc += nch[k];
-        ns += need[k];
-    }
-    ctx->relaxed = false;   // the popped slice is overwritten below
-    ctx->dd_built = false;
-    if (!ctx->frontier_reserve(base + nc, (size_t)(sol_start + ns))) return SGUFP_ERR_HIP;
-    const int np = (int)par.size();
-    if (np) {
-        int32_t *d_par = nullptr;
-        int64_t *d_dc = nullptr, *d_ds = nullptr;
-        if (np > ctx->max_batch) return SGUFP_ERR_STATE;
-        d_par = ctx->d_bidx;
-        d_dc = ctx->d_boff;
-        d_ds = ctx->d_bsol;
-        if (!ctx->upload(d_par, par.data(), np) || !ctx->upload(d_dc, dchild.data(), np) ||
-            !ctx->upload(d_ds, dsol.data(), np) ||
-            !ctx->hip_ok(launch_push_children(ctx->children_view(), o, d_par, d_dc, d_ds, np, ctx->fr, ctx->stream),
-                         "k_push_children") ||
-            !ctx->sync())
+    // Container::add for the cuts of the previous iteration's subproblems: their types and row
+    // bounds come down behind whatever the caller queued, one synchronisation, then the rows go
+    // under the feasibility list and the optimality list
+    int file_rows() {
+        const size_t np = prev.size();
+        ptype.resize(np);
+        pub.resize(np);
+        pobj.resize(np);
+        if (!c.download(ptype.data(), c.sio.cut_type, np) || !c.download(pub.data(), c.d_lrowub, np) ||
+            (c.trace && !c.download(pobj.data(), c.sio.obj_mean, np)) || !c.sync())
             return SGUFP_ERR_HIP;
-    }
-    ctx->fr_n = base + nc;
-    ctx->fr_sol_top = ctx->fr_n ? sol_start + ns : 0;
-    if (nd) {
-        // the deferred records on top, in their frontier order: popped first next round
-        int64_t stot = 0;
-        for (int i = 0; i < nd; i++) stot += d_len[i];
-        const int64_t e0 = ctx->fr_n, s0 = ctx->fr_sol_top;
-        if (!ctx->frontier_reserve(e0 + nd, (size_t)(s0 + stot))) return SGUFP_ERR_HIP;
-        std::vector<int64_t> so(nd);
-        std::vector<int16_t> flat;
-        flat.reserve((size_t)stot);
-        for (int i = 0; i < nd; i++) {
-            so[i] = s0 + (int64_t)flat.size();
-            flat.insert(flat.end(), d_sol[i].begin(), d_sol[i].end());
+        for (size_t i = 0; i < np; i++) {
+            if (ptype[i] < 0) {
+                // the rows of that launch leave the pool again (they were appended and
+                // applied on the device before the host saw the type); the batch's results
+                // are not used past the error
+                c.n_rows = prev_first;
+                c.err = "scenario subproblem failed (invalid path or numerical failure)";
+                return SGUFP_ERR_STATE;
+            }
         }
-        FrontierDev &f = ctx->fr;
-        if (!ctx->upload(f.gl + e0, d_gl.data(), nd) || !ctx->upload(f.lb + e0, d_lb.data(), nd) ||
-            !ctx->upload(f.ub + e0, d_ub.data(), nd) || !ctx->upload(f.mask + e0, d_mask.data(), nd) ||
-            !ctx->upload(f.valid + e0, d_valid.data(), nd) || !ctx->upload(f.sol_len + e0, d_len.data(), nd) ||
-            !ctx->upload(f.sol_off + e0, so.data(), nd) || !ctx->upload(f.sol + s0, flat.data(), flat.size()) ||
-            !ctx->sync())
-            return SGUFP_ERR_HIP;
-        ctx->fr_n = e0 + nd;
-        ctx->fr_sol_top = s0 + stot;
+        c.row_ub.resize((size_t)c.n_rows);
+        for (int want = 1; want >= 0; want--)
+            for (size_t i = 0; i < np; i++) {
+                if (ptype[i] != want) continue;
+                auto &list = want ? c.f_rows : c.o_rows;
+                if (c.trace) {
+                    auto &t = c.trace_items[1][prev_trace[i]];
+                    t.code = want;
+                    t.row = (int32_t)list.size();
+                    t.value = pobj[i];
+                }
+                list.push_back(prev_first + (int)i);
+                c.row_ub[(size_t)prev_first + i] = pub[i];
+                (want ? S.new_feasibility_cuts : S.new_optimality_cuts)++;
+            }
+        c.order_dirty = true;
+        prev.clear();
+        return SGUFP_OK;
     }
-    S.pushed = nc;
-    S.frontier = ctx->fr_n;
-    if (stats) *stats = S;
+
+    // With a round deadline, one iteration solves at most chunk_lps scenario LPs (a 1024-leaf
+    // iteration of the 512-scenario C5 network would take minutes): the fresh records past the
+    // chunk are returned -- they stay in the loop unchanged (path not yet seen) for the next
+    // iteration, or are deferred at the deadline -- and nct is recomputed over the kept ones
+    // (fresh holds the flag-2 records in loop order)
+    std::vector<int> split_chunk(std::vector<int> &fresh, int &nct) const {
+        const size_t chunk = (size_t)std::max<int64_t>(1, c.chunk_lps / std::max(1, c.net.S));
+        if (fresh.size() <= chunk) return {};
+        const std::vector<int> rest(fresh.begin() + (long)chunk, fresh.end());
+        fresh.resize(chunk);
+        nct = 1;
+        size_t kept_n = 0;
+        for (size_t a = 0; a < flag.size() && kept_n < chunk; a++)
+            if (flag[a] == 2) {
+                nct = std::max(nct, chains[a]);
+                kept_n++;
+            }
+        return rest;
+    }
+
+    // the subproblem launch on the nf fresh paths, read in place from the batch's outputs
+    bool sub_io(int nf, int nct, SubIO &io) {
+        io = c.sio;
+        io.n_paths = nf;
+        io.nct_cap = nct;
+        io.path_slot = c.d_lact;
+        io.path_len = o.path_len;
+        io.path_stride = c.sc.Lcap;
+        io.paths = o.path;
+        io.path_off = nullptr;
+        // warm starts: every path starts from the stored state of the closest path solved
+        // before (the record's own previous path, a sibling's, ...) and leaves its own state
+        // in the ring for the next ones (k_warm_pick, k_sub_scenario<..., WARM>)
+        if (!c.warm_reserve()) return true;
+        if (!c.hip_ok(launch_warm_pick(io, c.wring, c.warm_ptr, c.stream), "k_warm_pick")) return false;
+        io.warm_src = c.wring.src;
+        io.warm_dst = c.wring.dst;
+        io.wst_x = c.d_wx;
+        io.wst_a = c.d_wa;
+        io.wst_ok = c.d_wok;
+        c.warm_ptr = (c.warm_ptr + nf) % c.wring.R;
+        return true;
+    }
+
+    // ---- 4: the deferred records, saved before the children overwrite the popped slice, and
+    // their seen lists under the records' keys ----
+    int save_deferred() {
+        S.deferred = (int64_t)deferred.size();
+        if (deferred.empty()) return SGUFP_OK;
+        if (popped.gl.empty() && !c.read_frontier(base, b, popped)) return SGUFP_ERR_HIP;
+        for (size_t i = 0; i < deferred.size(); i++) {
+            kept.append(popped, deferred[i]);
+            kept.ub.back() = ub[deferred[i]];   // the bound the loop reached (every pool cut is valid)
+            c.deferred_seen[kept.key((int)i)] = std::move(seen_host[i]);
+        }
+        return SGUFP_OK;
+    }
+
+    // ---- 5: incumbent (DDSolver.cpp:723-731) ----
+    int update_incumbent() {
+        znew = z;
+        for (int k = 0; k < b; k++)
+            if (lbv[k] > znew) znew = lbv[k];
+        S.improved = znew > z ? 1 : 0;
+        incumbent = znew;
+        return SGUFP_OK;
+    }
+
+    // ---- 6: push the children of parents with ub > zOpt (DDSolver.cpp:744-748) ----
+    int push_children() {
+        std::vector<int32_t> par;
+        std::vector<int64_t> dchild, dsol;
+        int64_t nc = 0, ns = 0;
+        for (int k = 0; k < b; k++) {
+            if (st[k] != SGUFP_SUCCESS || nch[k] == 0 || !(ub[k] > znew)) continue;
+            par.push_back(k);
+            dchild.push_back(base + nc);
+            dsol.push_back(sol_start + ns);
+            nc += nch[k];
+            ns += need[k];
+        }
+        c.relaxed = false;   // the popped slice is overwritten below
+        c.dd_built = false;
+        if (!c.frontier_reserve(base + nc, (size_t)(sol_start + ns))) return SGUFP_ERR_HIP;
+        const int np = (int)par.size();
+        if (np > c.max_batch) return SGUFP_ERR_STATE;
+        if (np && (!c.upload(c.d_bidx, par.data(), np) || !c.upload(c.d_boff, dchild.data(), np) ||
+                   !c.upload(c.d_bsol, dsol.data(), np) ||
+                   !c.hip_ok(launch_push_children(c.children_view(), o, c.d_bidx, c.d_boff, c.d_bsol, np, c.fr, c.stream),
+                             "k_push_children") ||
+                   !c.sync()))
+            return SGUFP_ERR_HIP;
+        c.fr_n = base + nc;
+        c.fr_sol_top = c.fr_n ? sol_start + ns : 0;
+        S.pushed = nc;
+        return SGUFP_OK;
+    }
+
+    // ---- 7: the deferred records on top, in their frontier order: popped first next round ----
+    int push_deferred() {
+        if (!kept.gl.empty()) {
+            if (!c.write_frontier(c.fr_n, c.fr_sol_top, kept)) return SGUFP_ERR_HIP;
+            c.fr_n += (int64_t)kept.gl.size();
+            c.fr_sol_top += (int64_t)kept.sol.size();
+        }
+        S.frontier = c.fr_n;
+        return SGUFP_OK;
+    }
+};
+
+}  // namespace
+
+extern "C" int sgufp_bnb_step(sgufp_ctx *ctx, int max_nodes, double *incumbent, sgufp_bnb_stats *stats) {
+    if (!ctx || !incumbent) return SGUFP_ERR_ARG;
+    if (ctx->fr_n == 0) {
+        if (stats) *stats = sgufp_bnb_stats{};
+        return SGUFP_OK;
+    }
+    int b = ctx->max_batch;
+    if (max_nodes > 0) b = std::min(b, max_nodes);
+    BnbRound r(*ctx, *incumbent, (int)std::min<int64_t>(b, ctx->fr_n));
+    int rc;
+    if ((rc = r.pop_and_relax()) != SGUFP_OK || (rc = r.classify()) != SGUFP_OK || (rc = r.refine()) != SGUFP_OK ||
+        (rc = r.save_deferred()) != SGUFP_OK || (rc = r.update_incumbent()) != SGUFP_OK ||
+        (rc = r.push_children()) != SGUFP_OK || (rc = r.push_deferred()) != SGUFP_OK)
+        return rc;
+    if (stats) *stats = r.S;
     return SGUFP_OK;
 }
-
-}  // extern "C"

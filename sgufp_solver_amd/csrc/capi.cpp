@@ -232,12 +232,7 @@ bool sgufp_ctx::grow_children(size_t nchild, size_t nsol) {
             !alloc(d_cmask, child_cap, "children") || !alloc(d_csoloff, child_cap, "children"))
             return false;
     }
-    if (nsol > csol_cap) {
-        release(d_csol);
-        csol_cap = std::max(nsol, csol_cap * 2);
-        if (!alloc(d_csol, csol_cap, "children")) return false;
-    }
-    return true;
+    return grow(d_csol, csol_cap, nsol, "children");
 }
 
 static sgufp_ctx *finish_create(sgufp_ctx *ctx, int *err) {
@@ -505,24 +500,24 @@ bool sgufp_ctx::emit_current(const BatchIn &in, const Pool &p) {
 // universe in force at the record's layer, solutions packed; invalid records are flagged
 // (the kernels answer them with SGUFP_NODE_ERR_RECORD) rather than rejected.
 void sgufp_ctx::encode_records(int n, const uint16_t *gl, const int64_t *states_off, const int16_t *states,
-                               const int64_t *sol_off, const int16_t *sol, EncodedRecords &e) const {
+                               const int64_t *sol_off, const int16_t *sol, FrontierRecords &e) const {
     e.mask.assign(n, 0);
     e.valid.assign(n, 1);
-    e.soff.resize(n);
-    e.slen.resize(n);
+    e.off.resize(n);
+    e.len.resize(n);
     size_t total = 0;
     for (int k = 0; k < n; k++) {
         int64_t l = sol_off[k + 1] - sol_off[k];
         if (l < 0 || l > net.L) { e.valid[k] = 0; l = 0; }
-        e.soff[k] = (int64_t)total;
-        e.slen[k] = (uint16_t)l;
+        e.off[k] = (int64_t)total;
+        e.len[k] = (uint16_t)l;
         total += (size_t)l;
     }
-    e.sols.resize(total);
+    e.sol.resize(total);
     for (int k = 0; k < n; k++) {
-        if (e.slen[k]) std::memcpy(e.sols.data() + e.soff[k], sol + sol_off[k], e.slen[k] * sizeof(int16_t));
-        for (int t = 0; t < e.slen[k]; t++) {
-            int d = e.sols[e.soff[k] + t];
+        if (e.len[k]) std::memcpy(e.sol.data() + e.off[k], sol + sol_off[k], e.len[k] * sizeof(int16_t));
+        for (int t = 0; t < e.len[k]; t++) {
+            int d = e.sol[e.off[k] + t];
             if (d != -1 && (d < 0 || d >= net.m)) e.valid[k] = 0;
         }
         int g = gl[k];
@@ -1076,19 +1071,15 @@ int sgufp_batch_upload(sgufp_ctx *ctx, int n, const uint16_t *gl, const double *
                        const int64_t *states_off, const int16_t *states, const int64_t *sol_off, const int16_t *sol) {
     if (!ctx || n < 0 || n > ctx->max_batch || (n && (!gl || !lb || !ub || !states_off || !sol_off)))
         return SGUFP_ERR_ARG;
-    EncodedRecords e;
+    FrontierRecords e;
     ctx->encode_records(n, gl, states_off, states, sol_off, sol, e);
-    const size_t total = e.sols.size();
-    if (total > ctx->sol_cap) {
-        ctx->release(ctx->d_sol);
-        ctx->sol_cap = std::max(total, 2 * ctx->sol_cap);
-        if (!ctx->alloc(ctx->d_sol, ctx->sol_cap, "batch")) return SGUFP_ERR_HIP;
-    }
+    const size_t total = e.sol.size();
+    if (!ctx->grow(ctx->d_sol, ctx->sol_cap, total, "batch")) return SGUFP_ERR_HIP;
     ctx->n = n;
     if (!ctx->upload(ctx->d_gl, gl, n) || !ctx->upload(ctx->d_lb, lb, n) || !ctx->upload(ctx->d_ub, ub, n) ||
         !ctx->upload(ctx->d_mask, e.mask.data(), n) || !ctx->upload(ctx->d_valid, e.valid.data(), n) ||
-        !ctx->upload(ctx->d_soloff, e.soff.data(), n) || !ctx->upload(ctx->d_sollen, e.slen.data(), n) ||
-        !ctx->upload(ctx->d_sol, e.sols.data(), total) || !ctx->sync())
+        !ctx->upload(ctx->d_soloff, e.off.data(), n) || !ctx->upload(ctx->d_sollen, e.len.data(), n) ||
+        !ctx->upload(ctx->d_sol, e.sol.data(), total) || !ctx->sync())
         return SGUFP_ERR_HIP;
     ctx->cur = ctx->staged();
     ctx->relaxed = false;

@@ -66,12 +66,18 @@ struct DevBuf {
 
 }  // namespace
 
-struct EncodedRecords {
+// Host copies of frontier records in the device encoding (sgufp_ctx::read_frontier /
+// write_frontier / encode_records): the seven per-record arrays and the solutions packed in
+// entry order, `off` counting from the start of `sol`.
+struct FrontierRecords {
+    std::vector<uint16_t> gl, len;
+    std::vector<double> lb, ub;
     std::vector<uint32_t> mask;
     std::vector<uint8_t> valid;
-    std::vector<int64_t> soff;
-    std::vector<uint16_t> slen;
-    std::vector<int16_t> sols;
+    std::vector<int64_t> off;
+    std::vector<int16_t> sol;
+    std::string key(int k) const;                      // deferred-loop key of record k
+    void append(const FrontierRecords &r, int k);      // record k of r, behind the ones held
 };
 
 struct sgufp_ctx {
@@ -123,8 +129,11 @@ struct sgufp_ctx {
     // record (gl, state mask, solution): restored when the record is popped again
     std::unordered_map<std::string, std::vector<std::vector<int16_t>>> deferred_seen;
     static void make_record_key(uint16_t gl, uint32_t mask, const int16_t *sol, size_t len, std::string &key);
-    // keys of the frontier entries [lo, lo + count) (bulk downloads, one synchronisation)
-    bool slice_keys(int64_t lo, int count, std::vector<std::string> &keys);
+    // frontier entries [lo, lo + n) -> host (bulk downloads, two synchronisations)
+    bool read_frontier(int64_t lo, int n, FrontierRecords &r);
+    // records -> frontier entries from e0 on, solutions from arena position s0 on (reserves,
+    // uploads, synchronises; fr_n and fr_sol_top are the caller's)
+    bool write_frontier(int64_t e0, int64_t s0, const FrontierRecords &r);
     // round trace (sgufp_bnb_set_trace): what the last sgufp_bnb_step did, for tests
     bool trace = false;
     struct TraceItem {
@@ -149,7 +158,7 @@ struct sgufp_ctx {
     bool relax_current(double optimal_lb);
     bool relax_order(BatchIn &in);
     void encode_records(int n, const uint16_t *gl, const int64_t *states_off, const int16_t *states,
-                        const int64_t *sol_off, const int16_t *sol, EncodedRecords &e) const;
+                        const int64_t *sol_off, const int16_t *sol, FrontierRecords &e) const;
     // device records [count] (mask over the layer's universe) -> host states, as sgufp_batch_children
     void decode_states(const uint16_t *gl, const uint32_t *mask, size_t count, int64_t *states_off,
                        int16_t *states) const;
@@ -320,6 +329,14 @@ struct sgufp_ctx {
         return hip_ok(hipMemcpyAsync(dst, src, count * sizeof(T), hipMemcpyDeviceToHost, stream), "D2H");
     }
     bool sync() { return hip_ok(hipStreamSynchronize(stream), "stream sync"); }
+    // a device buffer of at least `need` entries; its contents do not survive growing
+    template <typename T>
+    bool grow(T *&p, size_t &cap, size_t need, const char *what) {
+        if (need <= cap && p) return true;
+        if (p) release(p);
+        cap = std::max(need, 2 * cap);
+        return alloc(p, cap, what);
+    }
 
     bool init();
     bool grow_rows(int need);

@@ -89,14 +89,6 @@ bool nccl_ok(sgufp_ctx *ctx, ncclResult_t r, const char *what) {
     return false;
 }
 
-template <typename T>
-bool grow(sgufp_ctx *ctx, T *&p, size_t &cap, size_t need, const char *what) {
-    if (need <= cap && p) return true;
-    if (p) ctx->release(p);
-    cap = std::max(need, 2 * cap);
-    return ctx->alloc(p, cap, what);
-}
-
 }  // namespace
 
 namespace sgufp {
@@ -281,7 +273,7 @@ bool sgufp_ctx::frontier_drop_bottom(int64_t g) {
     if (!download(&s_hi, fr.sol_off + g, 1) || !sync()) return false;
     const size_t srest = (size_t)(fr_sol_top - s_hi);
     const size_t need = std::max(rest * 8, srest * 2);
-    if (!grow(this, bounce, bounce_cap, std::max<size_t>(need, 8), "bounce")) return false;
+    if (!grow(bounce, bounce_cap, std::max<size_t>(need, 8), "bounce")) return false;
     auto move = [&](void *dst, const void *src, size_t bytes) {
         return bytes == 0 || (hip_ok(hipMemcpyAsync(bounce, src, bytes, hipMemcpyDeviceToDevice, stream), "D2D") &&
                               hip_ok(hipMemcpyAsync(dst, bounce, bytes, hipMemcpyDeviceToDevice, stream), "D2D"));
@@ -402,10 +394,10 @@ int sgufp_cuts_exchange(sgufp_ctx *ctx, int64_t *received) {
         const int64_t kmax = *std::max_element(ks.begin(), ks.end());
         if (kmax == 0) continue;
         const size_t block = (size_t)kmax * blk;
-        if (!grow(ctx, ctx->d_xsend, ctx->xsend_cap, block, "cut exchange") ||
-            !grow(ctx, ctx->d_xrecv, ctx->xrecv_cap, block * W, "cut exchange") ||
-            !grow(ctx, ctx->d_xids, ctx->xids_cap, (size_t)std::max<int64_t>(k, 1), "cut exchange") ||
-            !grow(ctx, ctx->d_xub, ctx->xub_cap, (size_t)kmax, "cut exchange"))
+        if (!ctx->grow(ctx->d_xsend, ctx->xsend_cap, block, "cut exchange") ||
+            !ctx->grow(ctx->d_xrecv, ctx->xrecv_cap, block * W, "cut exchange") ||
+            !ctx->grow(ctx->d_xids, ctx->xids_cap, (size_t)std::max<int64_t>(k, 1), "cut exchange") ||
+            !ctx->grow(ctx->d_xub, ctx->xub_cap, (size_t)kmax, "cut exchange"))
             return SGUFP_ERR_HIP;
         if (k > 0 && (!ctx->upload(ctx->d_xids, v.data() + mark, (size_t)k) ||
                       !ctx->hip_ok(launch_gather_rows(ctx->d_rows, ctx->d_rhs, ctx->d_xids, (int)k, stride, ctx->d_xsend,
@@ -451,9 +443,9 @@ int sgufp_frontier_balance(sgufp_ctx *ctx, int64_t *received) {
     auto chunk = [&](int r, int j, int64_t &lo, int64_t &hi) { chunk_of(give[r], j, ni, lo, hi); };
     // the given records leave this context: their deferred loops' seen lists go no further
     if (give[me] > 0 && !ctx->deferred_seen.empty()) {
-        std::vector<std::string> keys;
-        if (!ctx->slice_keys(0, (int)give[me], keys)) return SGUFP_ERR_HIP;
-        for (auto &k : keys) ctx->deferred_seen.erase(k);
+        FrontierRecords r;
+        if (!ctx->read_frontier(0, (int)give[me], r)) return SGUFP_ERR_HIP;
+        for (int k = 0; k < (int)give[me]; k++) ctx->deferred_seen.erase(r.key(k));
     }
     // solution spans of this shard's chunks: [sol_lo, sol_hi) per idle shard
     std::vector<int64_t> span((size_t)2 * ni, 0);
@@ -476,7 +468,7 @@ int sgufp_frontier_balance(sgufp_ctx *ctx, int64_t *received) {
         const int per = 2 * W;
         std::vector<int64_t> mine_sp((size_t)per, 0);
         std::copy(span.begin(), span.end(), mine_sp.begin());
-        if (!grow(ctx, ctx->d_xspan, ctx->xspan_cap, (size_t)per * (W + 1), "balance")) return SGUFP_ERR_HIP;
+        if (!ctx->grow(ctx->d_xspan, ctx->xspan_cap, (size_t)per * (W + 1), "balance")) return SGUFP_ERR_HIP;
         int64_t *send = ctx->d_xspan + (size_t)per * W;
         all_span.assign((size_t)per * W, 0);
         if (!ctx->upload(send, mine_sp.data(), (size_t)per) ||

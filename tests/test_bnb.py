@@ -126,6 +126,52 @@ def test_bnb_deferred_refinement_keeps_the_optimum(iters, batch):
     assert solver.counters["deferred"] > 0
 
 
+def test_deferred_records_return_on_top_unchanged():
+    """Round by round under a one-iteration limit: the records a round defers come back on top
+    of the frontier, in their frontier order, bit for bit what was popped (gl, lb, states,
+    solution) with a bound no greater than before; the counters add up; a round resumes no more
+    loops than the round before deferred; and the search ends at the extensive-form optimum."""
+    inst, path = _inst("T4", 3, 3)
+    opt = ef.solve(inst)
+    eng = E.Engine(path, 0, 256)
+    eng.bnb_set_limits(1, 0.0)
+    eng.frontier_clear()
+    eng.frontier_push([NodeRecord(0, DOUBLE_MIN, DOUBLE_MAX, [], [])])
+
+    def records(b):
+        return [(int(b.gl[k]), b.lb[k:k + 1].tobytes(), b.states[b.states_off[k]:b.states_off[k + 1]].tobytes(),
+                 b.sol[b.sol_off[k]:b.sol_off[k + 1]].tobytes()) for k in range(b.n)]
+
+    z = DOUBLE_MIN
+    deferred_rounds = resumed = 0
+    last_deferred = None
+    for _ in range(2000):
+        size = eng.frontier_size()
+        if size == 0:
+            break
+        n = min(64, size)
+        before = eng.frontier_peek(size - n, n)
+        z, st = eng.bnb_step(z, 64)
+        assert st.frontier == size - st.popped + st.pushed + st.deferred == eng.frontier_size()
+        if last_deferred is not None:
+            assert st.resumed <= last_deferred
+        resumed += st.resumed
+        last_deferred = st.deferred if st.deferred > 0 else None
+        if st.deferred > 0:
+            deferred_rounds += 1
+            after = eng.frontier_peek(st.frontier - st.deferred, st.deferred)
+            old = records(before)
+            at = -1
+            for k, rec in enumerate(records(after)):
+                # the next pre-round record equal to it: the same relative order
+                at = next((j for j in range(at + 1, n) if old[j] == rec), None)
+                assert at is not None, (k, rec)
+                assert after.ub[k] <= before.ub[at]
+    eng.close()
+    assert deferred_rounds > 0 and resumed > 0
+    assert abs(z - opt) <= TOL * max(1.0, abs(opt))
+
+
 def test_tiny_round_deadline_still_progresses():
     """A round deadline shorter than the relaxation itself (sgufp_bnb_set_limits with 1 us):
     every round still runs one refinement iteration, so deferred loops advance and the search
