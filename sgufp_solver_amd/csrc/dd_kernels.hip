@@ -797,12 +797,6 @@ struct BatchView {
     GBL double *s2b;       // HBM [tail_cap][CB]: layers >= kg
     GBL double *sm, *xm;   // HBM [Tcap][CB]
     uint32_t gbase;    // noff[kg]
-#ifdef SGUFP_PROF
-    uint64_t prof[2];  // ticks: coefficient staging, merged layers
-#endif
-#ifdef SGUFP_TRACE
-    int trace_on;
-#endif
 };
 
 
@@ -1068,16 +1062,10 @@ __device__ __forceinline__ void sweep_narrow(const NetDev &net, DD &d, BatchView
     const int ke = min(d.kg, kend);   // layers >= kend are not needed (exact redo)
     for (int k = 1; k < ke;) {
         if (k == k1) {
-#ifdef SGUFP_PROF
-            const uint64_t t_sw = wall_clock64();
-#endif
             // next group: its words and coefficients were issued one group ago
             j++;
             slot ^= 1;
             commit(slot);
-#ifdef SGUFP_PROF_COMMIT
-            bv.prof[1] += wall_clock64() - t_sw;
-#endif
             k0 = k1;
             k1 = uni((int)d.gstart[j + 1]);
             const int k2 = j + 1 < d.ng ? uni((int)d.gstart[j + 2]) : k1;
@@ -1090,9 +1078,6 @@ __device__ __forceinline__ void sweep_narrow(const NetDev &net, DD &d, BatchView
             gnN = rl(m_noff, k1 - kw) - gn0;
             ga0 = rl(m_aoff, k0 - kw);
             wave_lds_sync();
-#ifdef SGUFP_PROF
-            bv.prof[0] += wall_clock64() - t_sw;
-#endif
         }
         const int l = k - k0, lm = k - kw;
         const LDS double *coefk = bv.cring + (size_t)slot * kStageEntries + (size_t)l * per_layer;
@@ -1103,9 +1088,6 @@ __device__ __forceinline__ void sweep_narrow(const NetDev &net, DD &d, BatchView
         LDS double *cbuf = bv.vb + (size_t)(k & 1) * kLdsBatchWidth * CB;
         const bool w1 = (pk >> 31) != 0;
         if (acnt) {
-#ifdef SGUFP_PROF
-            const uint64_t t_m = wall_clock64();
-#endif
             // state2 of the last batch cut: only what a path walk reads (merged nodes and
             // their parents) unless every layer is asked for (kS = T: the exact redo)
             const bool wr = ((pk >> 30) & 1u) != 0;
@@ -1204,9 +1186,6 @@ __device__ __forceinline__ void sweep_narrow(const NetDev &net, DD &d, BatchView
                 }
             }
             wave_lds_sync();
-#ifdef SGUFP_PROF
-            bv.prof[1] += wall_clock64() - t_m;
-#endif
             k++;
             continue;
         }
@@ -1227,9 +1206,6 @@ __device__ __forceinline__ void sweep_narrow(const NetDev &net, DD &d, BatchView
         wave_lds_sync();
         k = kb + 1;
     }
-#ifdef SGUFP_TRACE
-    bv.trace_on = 0;
-#endif
 }
 
 // value of node p of layer k for batch cut c (LDS for narrow layers, HBM for the tail)
@@ -1259,49 +1235,63 @@ __device__ __forceinline__ ParentVals<CB, PV_LDS> parent_vals(const DD &d, const
 }
 
 // Wide layers (k >= kg) stream through HBM: one node per lane per item, U items per lane
-// per step, the CB cut values of a node in registers.  Software pipeline: the topology
-// words of step s + 1 are in flight while step s loads its parent values, and the parent
-// values of step s + 1 while step s computes (loads issued back to back, fenced).
+// per step, the CB cut values of a node in registers.  stream_wide is the software pipeline
+// of a pass over a wide layer: the values of a middle layer (sweep_tail_layer) and the leaf
+// pass of the screening sweep (screen_leaf) run on it.  fused_leaf_t and f_leaf_scan_t carry
+// the same loop written out, because k_relax sits at 256 VGPRs and on the helper their
+// register allocation came out measurably slower; a change to the loop goes into all three.
+// Three steps are in flight: while
+// step s computes, the parent values of step s + 1 and the topology words and flags of
+// step s + 2 are loading.  Items past the layer end read node 0 and carry flag 0 (not
+// alive).  A step issues its loads back to back (parent values and the optional per-node
+// side value side(i) of step s + 1, topology of step s + 2, the coefficients cf[u][c] of
+// its own nodes), then a scheduling fence, then calls
+//     body(i, topo, flag, px[CB], cf[CB], side_value)
+// for each of its U nodes, dead or past the end included; the body's stores therefore
+// come after the fence.  Passes without a side value give NoSide, which costs nothing.
+// The caller does its own reductions and its wave_mem_sync().
 template <int CB>
 struct WideTopo {
     static constexpr int U = CB >= 8 ? 1 : 16 / CB;
     uint32_t t[U], f[U];
 };
 
-template <int CB, bool PV_LDS>
-__device__ __forceinline__ void sweep_tail_layer_t(const NetDev &net, DD &d, BatchView &bv, const Pool &pool, int k, int nb,
-                                                   int kS) {
+struct NoSide {
+    __device__ __forceinline__ double operator()(uint32_t) const { return 0.0; }
+};
+
+template <int CB, bool PV_LDS, typename Side, typename Body>
+__device__ __forceinline__ void stream_wide(const DD &d, const BatchView &bv, int us, int k, Side side, Body body) {
     constexpr int U = WideTopo<CB>::U;
     constexpr uint32_t STEP = (uint32_t)U * kWave;
-    batch_coef_direct(net, d, bv, pool, k, nb);
-    const int us = pool.ustride;
-    const uint32_t noff = uni(d.noff[k]), n = uni(d.nn[k]);
-    // state2 of tail layers is read only by the exact redo (its write mask, or kS = T)
-    const bool w1 = uni(bv.w1[k]) != 0;
-    const bool wr = bv.wsel ? ((bv.wsel[k >> 6] >> (k & 63)) & 1ull) != 0 : kS >= d.T;
+    const uint32_t lo = uni(d.noff[k]), ln = uni(d.nn[k]);
     const ParentVals<CB, PV_LDS> pv = parent_vals<CB, PV_LDS>(d, bv, k - 1);
-    GBL double *out = bv.s2b + (size_t)(noff - bv.gbase) * CB;
     auto load_topo = [&](uint32_t base, WideTopo<CB> &tp) {
 #pragma unroll
         for (int u = 0; u < U; u++) {
             const uint32_t i = base + (uint32_t)u * kWave + lane();
-            const uint32_t ic = i < n ? i : 0u;
-            tp.t[u] = d.ntopo[noff + ic];
-            tp.f[u] = i < n ? (uint32_t)d.nflag[noff + ic] : 0u;
+            const uint32_t ic = i < ln ? i : 0u;
+            tp.t[u] = d.ntopo[lo + ic];
+            tp.f[u] = i < ln ? (uint32_t)d.nflag[lo + ic] : 0u;
         }
     };
-    auto load_px = [&](const WideTopo<CB> &tp, double (&px)[U][CB]) {
+    auto load_px = [&](uint32_t base, const WideTopo<CB> &tp, double (&px)[U][CB], double (&sv)[U]) {
 #pragma unroll
-        for (int u = 0; u < U; u++) pv.load((tp.f[u] & kAlive) ? (tp.t[u] & kParentMask) : 0u, px[u]);
+        for (int u = 0; u < U; u++) {
+            const uint32_t i = base + (uint32_t)u * kWave + lane();
+            const uint32_t ic = i < ln ? i : 0u;
+            pv.load((tp.f[u] & kAlive) ? (tp.t[u] & kParentMask) : 0u, px[u]);
+            sv[u] = side(ic);
+        }
     };
     WideTopo<CB> ta, tb;
-    double pxa[U][CB];
+    double pxa[U][CB], sa[U];
     load_topo(0, ta);
-    load_px(ta, pxa);
+    load_px(0, ta, pxa, sa);
     load_topo(STEP, tb);
-    for (uint32_t base = 0; base < n; base += STEP) {
-        double pxb[U][CB];
-        load_px(tb, pxb);
+    for (uint32_t base = 0; base < ln; base += STEP) {
+        double pxb[U][CB], sb[U];
+        load_px(base + STEP, tb, pxb, sb);
         WideTopo<CB> tn;
         load_topo(base + 2 * STEP, tn);
         double cf[U][CB];
@@ -1311,15 +1301,38 @@ __device__ __forceinline__ void sweep_tail_layer_t(const NetDev &net, DD &d, Bat
             for (int c = 0; c < CB; c++) cf[u][c] = bv.coef[c * us + (ta.t[u] >> kRankShift)];
         sched_fence();
 #pragma unroll
+        for (int u = 0; u < U; u++) body(base + (uint32_t)u * kWave + lane(), ta.t[u], ta.f[u], pxa[u], cf[u], sa[u]);
+        ta = tb;
+        tb = tn;
+#pragma unroll
         for (int u = 0; u < U; u++) {
-            const uint32_t i = base + (uint32_t)u * kWave + lane();
-            if (!(ta.f[u] & kAlive)) continue;
-            const uint32_t r = ta.t[u] >> kRankShift;
-            const bool inal = (ta.f[u] & kInAlive) != 0;
+            sa[u] = sb[u];
+#pragma unroll
+            for (int c = 0; c < CB; c++) pxa[u][c] = pxb[u][c];
+        }
+    }
+}
+
+// values of wide middle layer k for the nb batch cuts, and its width-1 summaries
+template <int CB, bool PV_LDS>
+__device__ __forceinline__ void sweep_tail_layer_t(const NetDev &net, DD &d, BatchView &bv, const Pool &pool, int k, int nb,
+                                                   int kS) {
+    batch_coef_direct(net, d, bv, pool, k, nb);
+    const uint32_t noff = uni(d.noff[k]);
+    // state2 of tail layers is read only by the exact redo (its write mask, or kS = T)
+    const bool w1 = uni(bv.w1[k]) != 0;
+    const bool wr = bv.wsel ? ((bv.wsel[k >> 6] >> (k & 63)) & 1ull) != 0 : kS >= d.T;
+    GBL double *out = bv.s2b + (size_t)(noff - bv.gbase) * CB;
+    stream_wide<CB, PV_LDS>(
+        d, bv, pool.ustride, k, NoSide{},
+        [&](uint32_t i, uint32_t t, uint32_t f, const double (&px)[CB], const double (&cf)[CB], double) {
+            if (!(f & kAlive)) return;
+            const uint32_t r = t >> kRankShift;
+            const bool inal = (f & kInAlive) != 0;
             double x[CB];
 #pragma unroll
             for (int c = 0; c < CB; c++) {
-                x[c] = !inal ? DMIN : (r != 0 ? pxa[u][c] + cf[u][c] : pxa[u][c]);
+                x[c] = !inal ? DMIN : (r != 0 ? px[c] + cf[c] : px[c]);
                 out[(size_t)i * CB + c] = x[c];
             }
             if (wr) {
@@ -1333,18 +1346,11 @@ __device__ __forceinline__ void sweep_tail_layer_t(const NetDev &net, DD &d, Bat
                 for (int c = 0; c < CB; c++) {
                     if (c < nb) {
                         bv.sm[(size_t)k * CB + c] = x[c];
-                        bv.xm[(size_t)k * CB + c] = !inal ? DMAX : (r != 0 ? x[c] : pxa[u][c] + 0.0);
+                        bv.xm[(size_t)k * CB + c] = !inal ? DMAX : (r != 0 ? x[c] : px[c] + 0.0);
                     }
                 }
             }
-        }
-        ta = tb;
-        tb = tn;
-#pragma unroll
-        for (int u = 0; u < U; u++)
-#pragma unroll
-            for (int c = 0; c < CB; c++) pxa[u][c] = pxb[u][c];
-    }
+        });
     wave_mem_sync();
 }
 
@@ -1405,7 +1411,8 @@ __device__ __forceinline__ bool dd_prune_check(const DD &d, const BatchView &bv,
 // Pass A: per cut the terminal state after the running-min update and maxState; it
 // commits the terminal weights of all nb cuts (the common case) and keeps the previous
 // weights in `keep`.  Pass B, only when the replay stops inside the batch: the weights of
-// cuts 0 .. capply from the kept ones.  Streaming as in sweep_tail_layer_t.  The maxima
+// cuts 0 .. capply from the kept ones.  Streaming as in stream_wide, on its own copy of
+// the loop (see there).  The maxima
 // are plain maxima; the (value, priority) pick of the reference's ordered folds differs
 // from them only when a maximum is a zero, and then fused_leaf_pick recomputes that cut's
 // pick exactly.
@@ -1540,7 +1547,7 @@ __device__ __forceinline__ void fused_leaf(const DD &d, BatchView &bv, const Poo
     else fused_leaf_t<CB, PASS_A, false>(d, bv, pool, ncut, keep, term, mxs);
 }
 
-// Feasibility batch, last layer.  One streaming pass (as sweep_tail_layer_t) computes
+// Feasibility batch, last layer.  One streaming pass (as stream_wide, own copy) computes
 // every alive leaf's values for the nb batch cuts and the first batch cut that removes it
 // (state2 < -0.01, DD.cpp:3884-3889), stored as cut + 1 in nflag bits 3..7 (0: none);
 // per cut it counts the removals and takes maxState over the leaves that survive the cut.
@@ -1576,7 +1583,7 @@ __device__ __forceinline__ void f_leaf_scan_t(DD &d, BatchView &bv, const Pool &
     const int last = d.T - 1;
     const uint32_t lo = uni(d.noff[last]), ln = uni(d.nn[last]);
     const int us = pool.ustride;
-    const bool wr = kS >= d.T;   // state2 of the last batch cut, as sweep_tail_layer_t
+    const bool wr = kS >= d.T;   // state2 of the last batch cut, as sweep_tail_layer
     const ParentVals<CB, PV_LDS> pv = parent_vals<CB, PV_LDS>(d, bv, last - 1);
     uint32_t cnt[CB];
     double vmx[CB];
@@ -2083,61 +2090,20 @@ __device__ __forceinline__ bool redo_cut(const NetDev &net, DD &d, BatchView &bv
 // nothing happened (the screen writes no DD state the exact phase reads).
 
 // leaf values of the nb screening cuts: run[i] = min(run[i], v_c(i)); returns the max over
-// alive leaves of run (DMIN when none is alive).  Streaming as in sweep_tail_layer_t.
+// alive leaves of run (DMIN when none is alive).  The side value is the leaf's run.
 template <int CB, bool PV_LDS>
 __device__ __forceinline__ double screen_leaf_t(const DD &d, BatchView &bv, const Pool &pool, int nb, bool first,
-                                                GBL double *run) {
-    constexpr int U = WideTopo<CB>::U;
-    constexpr uint32_t STEP = (uint32_t)U * kWave;
-    const int last = d.T - 1;
-    const uint32_t lo = uni(d.noff[last]), ln = uni(d.nn[last]);
-    const int us = pool.ustride;
-    const ParentVals<CB, PV_LDS> pv = parent_vals<CB, PV_LDS>(d, bv, last - 1);
+                                              GBL double *run) {
     double best = -INFINITY;
-    auto load_topo = [&](uint32_t base, WideTopo<CB> &tp) {
-#pragma unroll
-        for (int u = 0; u < U; u++) {
-            const uint32_t i = base + (uint32_t)u * kWave + lane();
-            const uint32_t ic = i < ln ? i : 0u;
-            tp.t[u] = d.ntopo[lo + ic];
-            tp.f[u] = i < ln ? (uint32_t)d.nflag[lo + ic] : 0u;
-        }
-    };
-    auto load_px = [&](uint32_t base, const WideTopo<CB> &tp, double (&px)[U][CB], double (&m)[U]) {
-#pragma unroll
-        for (int u = 0; u < U; u++) {
-            const uint32_t i = base + (uint32_t)u * kWave + lane();
-            const uint32_t ic = i < ln ? i : 0u;
-            pv.load((tp.f[u] & kAlive) ? (tp.t[u] & kParentMask) : 0u, px[u]);
-            m[u] = first ? DMAX : run[(size_t)ic * CB];
-        }
-    };
-    WideTopo<CB> ta, tb;
-    double pxa[U][CB], ma[U];
-    load_topo(0, ta);
-    load_px(0, ta, pxa, ma);
-    load_topo(STEP, tb);
-    for (uint32_t base = 0; base < ln; base += STEP) {
-        double pxb[U][CB], mb[U];
-        load_px(base + STEP, tb, pxb, mb);
-        WideTopo<CB> tn;
-        load_topo(base + 2 * STEP, tn);
-        double cf[U][CB];
-#pragma unroll
-        for (int u = 0; u < U; u++)
-#pragma unroll
-            for (int c = 0; c < CB; c++) cf[u][c] = bv.coef[c * us + (ta.t[u] >> kRankShift)];
-        sched_fence();
-#pragma unroll
-        for (int u = 0; u < U; u++) {
-            const uint32_t i = base + (uint32_t)u * kWave + lane();
-            const bool alive = (ta.f[u] & kAlive) != 0, inal = (ta.f[u] & kInAlive) != 0;
-            const uint32_t r = ta.t[u] >> kRankShift;
-            double m = ma[u];
+    stream_wide<CB, PV_LDS>(
+        d, bv, pool.ustride, d.T - 1, [&](uint32_t ic) { return first ? DMAX : run[(size_t)ic * CB]; },
+        [&](uint32_t i, uint32_t t, uint32_t f, const double (&px)[CB], const double (&cf)[CB], double m) {
+            const bool alive = (f & kAlive) != 0, inal = (f & kInAlive) != 0;
+            const uint32_t r = t >> kRankShift;
 #pragma unroll
             for (int c = 0; c < CB; c++) {
                 if (c < nb) {
-                    const double v = !inal ? DMIN : ((r != 0) ? pxa[u][c] + cf[u][c] : pxa[u][c]);
+                    const double v = !inal ? DMIN : ((r != 0) ? px[c] + cf[c] : px[c]);
                     m = fmin(m, v);
                 }
             }
@@ -2145,16 +2111,7 @@ __device__ __forceinline__ double screen_leaf_t(const DD &d, BatchView &bv, cons
                 run[(size_t)i * CB] = m;
                 best = (m > best) ? m : best;
             }
-        }
-        ta = tb;
-        tb = tn;
-#pragma unroll
-        for (int u = 0; u < U; u++) {
-            ma[u] = mb[u];
-#pragma unroll
-            for (int c = 0; c < CB; c++) pxa[u][c] = pxb[u][c];
-        }
-    }
+        });
     best = lane_reduce<1>(best, [](double a, double b) { return (b > a) ? b : a; });
     wave_mem_sync();
     return best != -INFINITY ? best : DMIN;
@@ -2409,12 +2366,6 @@ __global__ void __launch_bounds__(kWave, 2) k_relax(NetDev net, Scratch sc, Batc
         d.tmir = sc.tmir + (size_t)slot * sc.tmir_cap;
         d.gstart = (LDS uint16_t *)(smem + cv.o_gs);
         BatchView bv;
-#ifdef SGUFP_TRACE
-        bv.trace_on = 1;
-#endif
-#ifdef SGUFP_PROF
-        bv.prof[0] = bv.prof[1] = 0;
-#endif
         bv.vb = (LDS double *)(smem + cv.o_buf);
         bv.cring = (LDS double *)(smem + cv.o_ring);
         bv.tring = (LDS uint16_t *)(smem + cv.o_tring);
@@ -2431,10 +2382,6 @@ __global__ void __launch_bounds__(kWave, 2) k_relax(NetDev net, Scratch sc, Batc
         const bool nxtry = ex.enabled && ex.nx && !ex.redo && !d.exact && pool.no >= ex.nx_min;
         if (d.stream) cut_loop_batched<CB>(net, d, sc, bv, pool, incumbent, st, efast, nxtry ? &ex : nullptr, slot, &nx_k0);
         else cut_loop_single(net, d, pool, incumbent, 0, st, efast);
-#if defined(SGUFP_PROF) && defined(SGUFP_PHASES)
-        st.ph[6] += bv.prof[0];
-        st.ph[7] += bv.prof[1];
-#endif
     } else {
         cut_loop_single(net, d, pool, incumbent, 0, st, efast);
     }
@@ -3046,13 +2993,13 @@ hipError_t launch_relax(const NetDev &net, const Scratch &sc, const BatchIn &in,
                         const BatchOut &out, double incumbent, int cb, const ExactIO &ex, int cus, hipStream_t st) {
     if (in.n <= 0) return hipSuccess;
     size_t lds = relax_lds_bytes(sc.Tcap, sc.Lcap, cb, sc.us);
-    switch (cb) {
-        case 4: hipLaunchKernelGGL(k_relax<4>, dim3(in.n), dim3(kWave), lds, st, net, sc, in, pool, out, incumbent, ex); break;
-        case 8: hipLaunchKernelGGL(k_relax<8>, dim3(in.n), dim3(kWave), lds, st, net, sc, in, pool, out, incumbent, ex); break;
-        case 16: hipLaunchKernelGGL(k_relax<16>, dim3(in.n), dim3(kWave), lds, st, net, sc, in, pool, out, incumbent, ex); break;
-        default: hipLaunchKernelGGL(k_relax<1>, dim3(in.n), dim3(kWave), lds, st, net, sc, in, pool, out, incumbent, ex); break;
-    }
-    hipError_t e = hipGetLastError();
+    // k_relax at the cut-batch size cb (1, 4, 8 or 16; anything else runs single-cut)
+    auto relax = [&](const ExactIO &io) {
+        const auto k = cb == 4 ? k_relax<4> : cb == 8 ? k_relax<8> : cb == 16 ? k_relax<16> : k_relax<1>;
+        hipLaunchKernelGGL(k, dim3(in.n), dim3(kWave), lds, st, net, sc, in, pool, out, incumbent, io);
+        return hipGetLastError();
+    };
+    hipError_t e = relax(ex);
     if (e != hipSuccess || !ex.enabled || ex.no <= 0) return e;
     // exact DDs handed off by k_relax: root folds, terminal weights, outcome
     if ((e = launch_exact(net, sc, ex, incumbent, cus, st)) != hipSuccess) return e;
@@ -3065,13 +3012,7 @@ hipError_t launch_relax(const NetDev &net, const Scratch &sc, const BatchIn &in,
     if ((e = hipGetLastError()) != hipSuccess) return e;
     ExactIO rx = ex;
     rx.redo = 1;
-    switch (cb) {
-        case 4: hipLaunchKernelGGL(k_relax<4>, dim3(in.n), dim3(kWave), lds, st, net, sc, in, pool, out, incumbent, rx); break;
-        case 8: hipLaunchKernelGGL(k_relax<8>, dim3(in.n), dim3(kWave), lds, st, net, sc, in, pool, out, incumbent, rx); break;
-        case 16: hipLaunchKernelGGL(k_relax<16>, dim3(in.n), dim3(kWave), lds, st, net, sc, in, pool, out, incumbent, rx); break;
-        default: hipLaunchKernelGGL(k_relax<1>, dim3(in.n), dim3(kWave), lds, st, net, sc, in, pool, out, incumbent, rx); break;
-    }
-    return hipGetLastError();
+    return relax(rx);
 }
 
 hipError_t launch_scan(const uint32_t *a, const uint32_t *b, int n, uint64_t *oa, uint64_t *ob, hipStream_t st) {
