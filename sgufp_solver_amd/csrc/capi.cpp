@@ -125,6 +125,7 @@ bool sgufp_ctx::init() {
     if (const char *e = getenv("SGUFP_LEAF_SPLIT")) leaf_split = std::max(0, atoi(e));
     if (const char *e = getenv("SGUFP_NX_MIN")) nx_min = std::max(1, atoi(e));
     if (const char *e = getenv("SGUFP_NX_SKIP")) nx_skip = std::max(0, atoi(e));
+    if (const char *e = getenv("SGUFP_REDO_SWEEP")) sc.redo_sweep = atoi(e) != 0;   // exact redos by sweep (A/B)
     int64_t acap = std::max<int64_t>(1, (int64_t)std::max(0, L - 4) * (kRelaxedMaxWidth - 1) * maxU);
     if (ncap > (int64_t)kParentMask || acap > (int64_t)0x7FFFFFFF) { err = "DD capacity beyond 22-bit indices"; return false; }
     sc.Ncap = (int)ncap;
@@ -136,6 +137,9 @@ bool sgufp_ctx::init() {
     sc.tmir_cap = cb > 1 ? (int)(sc.Ncap + sc.Acap) : 0;
     sc.tail_cap = (int)tail;
     sc.cb_max = cb;
+    // narrow layers (< kg, at most 127 nodes): the layers node_bound counts at 119 nodes each, and
+    // whichever of the last five expanding layers stay narrow
+    sc.nar_cap = (int)std::min<int64_t>(ncap, (int64_t)(kRelaxedMaxWidth - 1) * (std::max(0, L - 5) + 1) + 5 * 127 + 8);
     const size_t B = (size_t)max_batch;
     if (!alloc(sc.ntopo, B * sc.Ncap, "scratch") || !alloc(sc.nflag, B * sc.Ncap, "scratch") ||
         !alloc(sc.nmask, B * sc.Ncap, "scratch") || !alloc(sc.outcnt, B * sc.Ncap, "scratch") ||
@@ -147,7 +151,8 @@ bool sgufp_ctx::init() {
         !alloc(sc.v1, B * sc.Tcap, "scratch"))
         return false;
     if (cb > 1 && (!alloc(sc.s2b, B * sc.tail_cap * cb, "scratch") || !alloc(sc.sm, B * sc.Tcap * cb, "scratch") ||
-                   !alloc(sc.xm, B * sc.Tcap * cb, "scratch") || !alloc(sc.tmir, B * (size_t)sc.tmir_cap, "scratch")))
+                   !alloc(sc.xm, B * sc.Tcap * cb, "scratch") || !alloc(sc.tmir, B * (size_t)sc.tmir_cap, "scratch") ||
+                   !alloc(sc.s2n, B * sc.nar_cap * cb, "scratch")))
         return false;
     // outputs
     if (!alloc(out.status, B, "out") || !alloc(out.exact, B, "out") || !alloc(out.lb, B, "out") ||

@@ -774,8 +774,9 @@ __device__ __forceinline__ double dd_post_optimality(const NetDev &net, DD &d, c
 // Only width-1 arc pruning changes later sweeps: per (width-1 layer, cut) the sweep
 // records the single node's state2 and the smallest parent.state2 + weight over its
 // in-arcs; since rounding is monotone, "some arc is pruned" <=> fl(xmin + gain) <=
-// threshold.  When that fires (or deletions make a new width-1 layer) the cut is redone
-// with the exact single-cut path and the batch restarts after it.
+// threshold.  When that fires (or deletions make a new width-1 layer) the cut's pruning is
+// redone exactly (redo_cut: from the batch sweep's own values of that cut when the DD was not
+// edited since, else after a sweep with that cut alone) and the batch restarts after it.
 //
 // Layout during a batch: the narrow layers (< 128 nodes: every layer but the last
 // few) keep their CB values per node in LDS, and their packed 16-bit topology words and
@@ -796,6 +797,8 @@ struct BatchView {
     const LDS uint64_t *wsel;   // the write mask in force (null: the kS rule)
     GBL double *s2b;       // HBM [tail_cap][CB]: layers >= kg
     GBL double *sm, *xm;   // HBM [Tcap][CB]
+    GBL double *s2n;       // HBM [nar_cap][CB]: the narrow layers above a merged layer, kept by the
+                           // batch sweeps for redo_cut (null: an exact redo sweeps its cut again)
     uint32_t gbase;    // noff[kg]
 };
 
@@ -866,7 +869,10 @@ __device__ __forceinline__ void batch_coef_direct(const NetDev &net, const DD &d
 // s2 (single values of the batch's last cut, read later by path walks) is written for
 // layers < kS only: the cutset layer can only move up, and exact-layer steps of a walk
 // read no state2.
-template <int CB>
+// KEEP: a batch sweep whose cuts may be redone (cut_loop_batched) also stores into bv.s2n,
+// per batch cut, the values of every layer of several alive nodes above a merged layer: what
+// the width-1 pruning of that merged layer reads and no summary holds (see prune_layers).
+template <int CB, bool KEEP = false>
 __device__ __forceinline__ void sweep_narrow(const NetDev &net, DD &d, BatchView &bv, const Pool &pool, int nb,
                                              double rv, int kS, int kend = INT_MAX) {
     constexpr int G = kWave / CB;
@@ -902,7 +908,8 @@ __device__ __forceinline__ void sweep_narrow(const NetDev &net, DD &d, BatchView
     uint64_t mmask = 0;
     // bit 30 of the packed word: this layer's state2 (of the last batch cut) is written --
     // what a path walk reads (merged layers and their parents, above the cutset layer kS)
-    // or, in an exact redo, the layers of the write mask
+    // or, in an exact redo, the layers of the write mask; bit 29 (KEEP): the layer below is a
+    // merged layer and this one is not width-1, so its values of every batch cut go to bv.s2n
     auto load_meta = [&](int kw) {
         const int k = kw + lane();
         const bool ok = k < d.T;
@@ -915,7 +922,8 @@ __device__ __forceinline__ void sweep_narrow(const NetDev &net, DD &d, BatchView
         m_noff = no;
         m_aoff = ao;
         const bool wrl = bv.wsel ? ((wsw >> (kk & 63)) & 1ull) != 0 : (k < kS && (kS >= d.T || ac != 0 || an != 0));
-        m_pk = (nn < 255u ? nn : 255u) | ((ac & 0xFFFu) << 8) | (wrl ? 0x40000000u : 0u) | (w ? 0x80000000u : 0u);
+        m_pk = (nn < 255u ? nn : 255u) | ((ac & 0xFFFu) << 8) | (wrl ? 0x40000000u : 0u) | (w ? 0x80000000u : 0u) |
+               (KEEP && bv.s2n && an != 0 && !w ? 0x20000000u : 0u);
         mmask = __ballot(ok && ac != 0);
     };
     auto rl = [](uint32_t v, int l) -> uint32_t { return (uint32_t)__builtin_amdgcn_readlane((int)v, l); };
@@ -981,6 +989,8 @@ __device__ __forceinline__ void sweep_narrow(const NetDev &net, DD &d, BatchView
             wrs[s] = ((rl(m_pk, lw + s) >> 30) & 1u) != 0;
         }
         const uint32_t nlast = rl(m_pk, lw + D - 1) & 255u;
+        // only the run's last layer can lie above a merged layer (a merged layer ends the run)
+        const bool kpl = KEEP && ((rl(m_pk, lw + D - 1) >> 29) & 1u) != 0;
         const bool wlane = c == nb - 1;   // the lane whose cut's state2 the path walks read
         auto items = [&](auto Uc, uint32_t base) {
             constexpr int U = decltype(Uc)::value;
@@ -1039,6 +1049,7 @@ __device__ __forceinline__ void sweep_narrow(const NetDev &net, DD &d, BatchView
                         for (int s = 0; s < D; s++)
                             if (wrs[s]) d.s2[nofs[s] + (wl[u][s] >> 16)] = xs[s];
                     }
+                    if (kpl) bv.s2n[(size_t)(nofs[D - 1] + (wl[u][D - 1] >> 16)) * CB + c] = xv;
                 }
             }
         };
@@ -1917,9 +1928,14 @@ __device__ __forceinline__ void cut_loop_single(const NetDev &net, DD &d, const 
 // the layers are processed back to back with their loads batched and no hand-off in
 // between (removing them at once, as the reference's batchRemoveArcs, is the same).
 // Returns false when some layer would lose all of its incoming arcs.
-template <int CB>
-__device__ __forceinline__ bool prune_layers(const NetDev &net, DD &d, const BatchView &bv, const Pool &pool, int id, int first,
-                                             int end, double maxState, double thresh) {
+// BATCH: the state2 values are those the batch sweep computed for its cut c (root value rv).
+// The single node's is the layer's summary sm.  The layer above: a width-1 layer's only alive
+// node is the tail of every alive arc, and its value is that layer's summary (rv for the root);
+// a wide layer is in s2b; a narrow layer of several alive nodes lies above a merged layer and
+// was kept in s2n.  Otherwise the values are in d.s2, where the exact redo sweep wrote them.
+template <int CB, bool BATCH>
+__device__ __forceinline__ bool prune_layers(const NetDev &net, DD &d, const BatchView &bv, const Pool &pool, int id, int c,
+                                             double rv, int first, int end, double maxState, double thresh) {
     constexpr int U = 4;
     const int us = pool.ustride;
     const GBL double *ct = pool.coefT + (size_t)id * ((size_t)net.L * us);
@@ -1931,10 +1947,16 @@ __device__ __forceinline__ bool prune_layers(const NetDev &net, DD &d, const Bat
             b &= b - 1;
             const uint32_t pnoff = uni(d.noff[k - 1]), acnt = uni(d.acnt[k]);
             const GBL double *ck = ct + (size_t)(d.g + k - 1) * us;
+            // parent values: pv[p * ps], or the one value ps1 of a width-1 / root layer
+            const bool one = BATCH && (k == 1 || uni(bv.w1[k - 1]) != 0);
+            const double ps1 = !one ? 0.0 : (k == 1 ? rv : bv.sm[(size_t)(k - 1) * CB + c]);
+            const uint32_t ps = BATCH ? CB : 1;
+            const GBL double *pv = !BATCH ? d.s2 + pnoff
+                                   : (k - 1 >= d.kg ? bv.s2b + (size_t)(pnoff - bv.gbase) * CB : bv.s2n + (size_t)pnoff * CB) + c;
             uint32_t total = 0, pruned = 0;
             if (acnt) {
                 const uint32_t aoff = uni(d.aoff[k]);
-                const double gain = maxState - d.s2[uni(d.noff[k])];
+                const double gain = maxState - (BATCH ? bv.sm[(size_t)k * CB + c] : d.s2[uni(d.noff[k])]);
                 for (uint32_t base = 0; base < acnt; base += U * kWave) {
                     uint32_t fl[U], tp[U];
 #pragma unroll
@@ -1949,7 +1971,7 @@ __device__ __forceinline__ bool prune_layers(const NetDev &net, DD &d, const Bat
 #pragma unroll
                     for (int u = 0; u < U; u++) {
                         const uint32_t r = tp[u] >> kRankShift;
-                        px[u] = d.s2[pnoff + (tp[u] & kParentMask)];
+                        px[u] = one ? ps1 : pv[(size_t)(tp[u] & kParentMask) * ps];
                         w[u] = r == 0 ? 0.0 : ck[r];
                     }
                     sched_fence();
@@ -1972,7 +1994,8 @@ __device__ __forceinline__ bool prune_layers(const NetDev &net, DD &d, const Bat
                 const uint32_t M = layer_single(d, k);
                 const uint32_t t = d.ntopo[M], f = d.nflag[M];
                 const uint32_t p = t & kParentMask, r = t >> kRankShift;
-                const double sM = d.s2[M], px = d.s2[pnoff + p], w = r == 0 ? 0.0 : ck[r];
+                const double sM = BATCH ? bv.sm[(size_t)k * CB + c] : d.s2[M];
+                const double px = one ? ps1 : pv[(size_t)p * ps], w = r == 0 ? 0.0 : ck[r];
                 if (f & kInAlive) {
                     total = 1;
                     if (((px + w) + (maxState - sM)) <= thresh) {
@@ -2015,13 +2038,17 @@ __device__ __forceinline__ bool fire_layers(const DD &d, BatchView &bv, int c, i
     return any != 0;
 }
 
-// Exact redo of one cut whose width-1 pruning fires (batch cut c, pool row id): a sweep
-// with this cut alone, then the pruning (DD.cpp:3895-3928 / 3987-4021).  The pruning reads
-// state2 only in the firing layers and the layers above them; those are known before the
-// sweep from the batch summaries of cut c (same DD, same values), so the sweep writes
-// state2 of just those layers; the summaries the sweep recomputes must fire the same
-// layers (checked; otherwise the sweep is repeated writing every layer).  Returns false
-// when a width-1 layer would lose all of its incoming arcs.
+// Exact redo of one cut whose width-1 pruning fires (batch cut c, pool row id): the pruning
+// of DD.cpp:3895-3928 / 3987-4021 with this cut's own state2.  The pruning reads state2 only
+// in the firing layers and the layers above them, and those layers are known from the batch
+// summaries of cut c.
+// unchanged (no edit since the batch sweep: same DD, same values): the batch sweep already
+// holds what the pruning reads -- the single nodes' values are the summaries, the layers
+// above them are in s2b or were kept in s2n -- so nothing is swept again.
+// Otherwise (an earlier cut of a feasibility batch removed leaves), or when the engine has
+// no s2n: a sweep with this cut alone that writes state2 of just those layers; the summaries
+// it recomputes must fire the same layers (checked; otherwise the sweep is repeated writing
+// every layer).  Returns false when a width-1 layer would lose all of its incoming arcs.
 template <int CB>
 __device__ __forceinline__ bool redo_cut(const NetDev &net, DD &d, BatchView &bv, const Pool &pool, int c, int id,
                                          double rv1, int first, int end, double thresh, double maxState,
@@ -2029,6 +2056,24 @@ __device__ __forceinline__ bool redo_cut(const NetDev &net, DD &d, BatchView &bv
     const int last = d.T - 1;
     const int nw = (d.T + 63) / 64;
     fire_layers<CB>(d, bv, c, first, end, thresh, maxState);
+    if (unchanged && bv.s2n) {
+        // every firing layer must have the layer above it at hand (see prune_layers): a narrow
+        // layer of several alive nodes was kept only above a merged layer -- above a tree layer
+        // of one alive node there is none, the cascade leaves no childless parent
+        bool have = true;
+        for (int w = 0; w < nw; w++) {
+            uint64_t b = bv.fm[w];
+            while (b) {
+                const int k = w * 64 + (int)(__ffsll((unsigned long long)b) - 1);
+                b &= b - 1;
+                have &= k == 1 || k - 1 >= d.kg || uni(bv.w1[k - 1]) != 0 || uni(d.acnt[k]) != 0;
+            }
+        }
+        if (have) {
+            wave_mem_sync();
+            return prune_layers<CB, true>(net, d, bv, pool, id, c, rv1, first, end, maxState, thresh);
+        }
+    }
     for (int w = lane(); w < nw; w += kWave) {
         const uint64_t f = bv.fm[w], fn = w + 1 < nw ? bv.fm[w + 1] : 0ull;
         bv.wm[w] = f | (f >> 1) | (fn << 63);   // layer k fires -> write k and k - 1
@@ -2037,8 +2082,8 @@ __device__ __forceinline__ bool redo_cut(const NetDev &net, DD &d, BatchView &bv
     for (int k = lane(); k < d.T; k += kWave) bv.w1[k] = ((d.nalive[k]) == 1) ? 1 : 0;
     wave_lds_sync();
     if (unchanged) {
-        // no edit since the batch sweep: the fresh summaries equal the batch ones, so the
-        // fire mask stands and the sweep stops after the last layer it writes
+        // the fresh summaries equal the batch ones, so the fire mask stands and the sweep
+        // stops after the last layer it writes
         int kend = 0;
         for (int w = 0; w < nw; w++) {
             const uint64_t m = bv.wm[w];
@@ -2050,7 +2095,7 @@ __device__ __forceinline__ bool redo_cut(const NetDev &net, DD &d, BatchView &bv
         for (int k = max(d.kg, 1); k < min(last, kend); k++) sweep_tail_layer<CB>(net, d, bv, pool, k, 1, d.T);
         bv.wsel = nullptr;
         wave_mem_sync();
-        return prune_layers<CB>(net, d, bv, pool, id, first, end, maxState, thresh);
+        return prune_layers<CB, false>(net, d, bv, pool, id, 0, rv1, first, end, maxState, thresh);
     }
     for (int attempt = 0; attempt < 2; attempt++) {
         bv.wsel = bv.wm;
@@ -2070,7 +2115,7 @@ __device__ __forceinline__ bool redo_cut(const NetDev &net, DD &d, BatchView &bv
         for (int w = lane(); w < nw; w += kWave) bv.wm[w] = ~0ull;
         wave_lds_sync();
     }
-    return prune_layers<CB>(net, d, bv, pool, id, first, end, maxState, thresh);
+    return prune_layers<CB, false>(net, d, bv, pool, id, 0, rv1, first, end, maxState, thresh);
 }
 
 // CB cuts of one type per sweep, replayed in pool order (see "Multi-cut sweeps")
@@ -2194,7 +2239,7 @@ __device__ __forceinline__ void cut_loop_batched(const NetDev &net, DD &d, const
         const double rv = root_fold_seq(pool, d, s, total);
         wave_lds_sync();
         st.stamp(4);
-        sweep_narrow<CB>(net, d, bv, pool, nb, rv, kS);
+        sweep_narrow<CB, true>(net, d, bv, pool, nb, rv, kS);
         st.stamp(1);
         if (d.kg == 0 && lane() < nb) bv.s2b[lane()] = rv;
         for (int k = max(d.kg, 1); k < last; k++) sweep_tail_layer<CB>(net, d, bv, pool, k, nb, kS);
@@ -2379,6 +2424,7 @@ __global__ void __launch_bounds__(kWave, 2) k_relax(NetDev net, Scratch sc, Batc
         bv.sm = sc.sm + (size_t)slot * sc.Tcap * CB;
         bv.xm = sc.xm + (size_t)slot * sc.Tcap * CB;
         build_stream(d, n_merged, CB * pool.ustride);   // tmir_cap = Ncap + Acap >= Nn + Amir
+        bv.s2n = (sc.redo_sweep || d.Nn > (uint32_t)sc.nar_cap) ? nullptr : sc.s2n + (size_t)slot * sc.nar_cap * CB;
         const bool nxtry = ex.enabled && ex.nx && !ex.redo && !d.exact && pool.no >= ex.nx_min;
         if (d.stream) cut_loop_batched<CB>(net, d, sc, bv, pool, incumbent, st, efast, nxtry ? &ex : nullptr, slot, &nx_k0);
         else cut_loop_single(net, d, pool, incumbent, 0, st, efast);

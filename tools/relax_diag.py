@@ -71,6 +71,9 @@ def main():
         m = st == s
         print(f"  status {s}: n={m.sum()} us/node {us[m].mean():.1f} sweeps {sw[m].mean():.1f} "
               f"us/sweep {np.mean(us[m] / np.maximum(sw[m], 1)):.2f} redo {redo[m].mean():.2f}")
+    slow = us >= np.percentile(us, 90)
+    print(f"redo per record: mean {redo.mean():.2f} max {redo.max()} slowest decile mean {redo[slow].mean():.2f} "
+          f"(sweeps {sw[slow].mean():.1f}, us {us[slow].mean():.0f}); records with a redo {np.mean(redo > 0):.3f}")
     ph = eng.phases() / 100.0
     names = ["build", "narrow", "tail", "last", "post", "redo", "finish", "epilog"]
     print("phase us/node: " + ", ".join(f"{nm} {ph[:, k].mean():.0f}" for k, nm in enumerate(names)))
