@@ -160,6 +160,12 @@ int sgufp_dd_cutset(sgufp_ctx *ctx, int node, double ub, int64_t *n_children);
 int sgufp_batch_debug(sgufp_ctx *ctx, int64_t *ticks, int32_t *redo);
 /* ticks per phase [n * 8]: build, narrow sweep, tail layers, last layer, replay/post, redo, finish, tail */
 int sgufp_batch_phases(sgufp_ctx *ctx, int64_t *phase);
+/* Refolds of the exact redos in the last relax (a context created under SGUFP_REFOLD_STATS=1,
+ * else SGUFP_ERR_STATE), [n * 16] per node: 0 refolds (a narrow layer above a firing merged layer
+ * folded again from the nearest width-1 summary), 1 layers refolded, 2 the deepest refold, 3 the
+ * most refolds in one redo, 4 refolds in feasibility batches, 5 redos with a refold, 6 + d refolds
+ * of d layers (15: nine or more).  The counters change no result. */
+int sgufp_batch_refold_stats(sgufp_ctx *ctx, uint32_t *stats);
 
 /* Which kernels took each node's optimality phase in the last sgufp_batch_relax (parity
  * tests of the cut-parallel phases at the pool sizes the B&B reaches; any staged node):

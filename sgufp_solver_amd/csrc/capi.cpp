@@ -137,9 +137,6 @@ bool sgufp_ctx::init() {
     sc.tmir_cap = cb > 1 ? (int)(sc.Ncap + sc.Acap) : 0;
     sc.tail_cap = (int)tail;
     sc.cb_max = cb;
-    // narrow layers (< kg, at most 127 nodes): the layers node_bound counts at 119 nodes each, and
-    // whichever of the last five expanding layers stay narrow
-    sc.nar_cap = (int)std::min<int64_t>(ncap, (int64_t)(kRelaxedMaxWidth - 1) * (std::max(0, L - 5) + 1) + 5 * 127 + 8);
     const size_t B = (size_t)max_batch;
     if (!alloc(sc.ntopo, B * sc.Ncap, "scratch") || !alloc(sc.nflag, B * sc.Ncap, "scratch") ||
         !alloc(sc.nmask, B * sc.Ncap, "scratch") || !alloc(sc.outcnt, B * sc.Ncap, "scratch") ||
@@ -151,9 +148,11 @@ bool sgufp_ctx::init() {
         !alloc(sc.v1, B * sc.Tcap, "scratch"))
         return false;
     if (cb > 1 && (!alloc(sc.s2b, B * sc.tail_cap * cb, "scratch") || !alloc(sc.sm, B * sc.Tcap * cb, "scratch") ||
-                   !alloc(sc.xm, B * sc.Tcap * cb, "scratch") || !alloc(sc.tmir, B * (size_t)sc.tmir_cap, "scratch") ||
-                   !alloc(sc.s2n, B * sc.nar_cap * cb, "scratch")))
+                   !alloc(sc.xm, B * sc.Tcap * cb, "scratch") || !alloc(sc.tmir, B * (size_t)sc.tmir_cap, "scratch")))
         return false;
+    // per-slot refold diagnostics of the exact redos (sgufp_batch_refold_stats; off by default)
+    if (const char *e = getenv("SGUFP_REFOLD_STATS"))
+        if (atoi(e) != 0 && cb > 1 && !alloc(sc.rstat, B * kRefoldStats, "scratch")) return false;
     // outputs
     if (!alloc(out.status, B, "out") || !alloc(out.exact, B, "out") || !alloc(out.lb, B, "out") ||
         !alloc(out.ub, B, "out") || !alloc(out.nchild, B, "out") || !alloc(out.sol_need, B, "out") ||
@@ -1331,6 +1330,13 @@ int sgufp_batch_phases(sgufp_ctx *ctx, int64_t *phase) {
     std::vector<uint64_t> t((size_t)ctx->n * 8);
     if (!ctx->download(t.data(), ctx->out.phase, t.size()) || !ctx->sync()) return SGUFP_ERR_HIP;
     for (size_t k = 0; k < t.size(); k++) phase[k] = (int64_t)t[k];
+    return SGUFP_OK;
+}
+
+int sgufp_batch_refold_stats(sgufp_ctx *ctx, uint32_t *stats) {
+    if (!ctx || !stats) return SGUFP_ERR_ARG;
+    if (!ctx->relaxed || !ctx->sc.rstat) return SGUFP_ERR_STATE;
+    if (!ctx->download(stats, ctx->sc.rstat, (size_t)ctx->n * kRefoldStats) || !ctx->sync()) return SGUFP_ERR_HIP;
     return SGUFP_OK;
 }
 

@@ -94,12 +94,14 @@ struct Scratch {
     double SGUFP_GBL *xm;        // [Tcap * cb_max]
     int tmir_cap;                // packed narrow-layer topology words per slot (Ncap + Acap)
     uint16_t SGUFP_GBL *tmir;    // [tmir_cap]
-    // batch values of the narrow layers above a merged layer (what its width-1 pruning reads,
-    // see redo_cut in dd_kernels.hip); a DD with more narrow nodes than nar_cap redoes by sweep
-    int nar_cap;                 // nodes of the layers < kg (at most 127 each)
-    double SGUFP_GBL *s2n;       // [nar_cap * cb_max]
     int redo_sweep;              // 1: every exact redo sweeps its cut again (SGUFP_REDO_SWEEP, A/B)
+    // diagnostics of the exact redos' refolds (see refold_parent in dd_kernels.hip), [kRefoldStats]
+    // per slot, null unless SGUFP_REFOLD_STATS=1: 0 refolds, 1 layers refolded, 2 deepest refold,
+    // 3 most refolds in one redo, 4 refolds in feasibility batches, 5 redos with a refold,
+    // 6 + d refolds of depth d (the last entry: that depth or deeper)
+    uint32_t SGUFP_GBL *rstat;
 };
+constexpr int kRefoldStats = 16;
 
 // Staged batch of open nodes (Inavap::Node records, DD.h:456-478), SoA.
 struct BatchIn {

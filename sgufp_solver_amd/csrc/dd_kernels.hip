@@ -797,8 +797,7 @@ struct BatchView {
     const LDS uint64_t *wsel;   // the write mask in force (null: the kS rule)
     GBL double *s2b;       // HBM [tail_cap][CB]: layers >= kg
     GBL double *sm, *xm;   // HBM [Tcap][CB]
-    GBL double *s2n;       // HBM [nar_cap][CB]: the narrow layers above a merged layer, kept by the
-                           // batch sweeps for redo_cut (null: an exact redo sweeps its cut again)
+    GBL uint32_t *rstat;   // this slot's refold diagnostics (Scratch::rstat), or null
     uint32_t gbase;    // noff[kg]
 };
 
@@ -869,10 +868,10 @@ __device__ __forceinline__ void batch_coef_direct(const NetDev &net, const DD &d
 // s2 (single values of the batch's last cut, read later by path walks) is written for
 // layers < kS only: the cutset layer can only move up, and exact-layer steps of a walk
 // read no state2.
-// KEEP: a batch sweep whose cuts may be redone (cut_loop_batched) also stores into bv.s2n,
-// per batch cut, the values of every layer of several alive nodes above a merged layer: what
-// the width-1 pruning of that merged layer reads and no summary holds (see prune_layers).
-template <int CB, bool KEEP = false>
+// Nothing else of the narrow layers leaves LDS: the values an exact redo needs of a narrow
+// layer above a firing merged layer are folded again from the nearest width-1 summary
+// (refold_parent).
+template <int CB>
 __device__ __forceinline__ void sweep_narrow(const NetDev &net, DD &d, BatchView &bv, const Pool &pool, int nb,
                                              double rv, int kS, int kend = INT_MAX) {
     constexpr int G = kWave / CB;
@@ -908,8 +907,7 @@ __device__ __forceinline__ void sweep_narrow(const NetDev &net, DD &d, BatchView
     uint64_t mmask = 0;
     // bit 30 of the packed word: this layer's state2 (of the last batch cut) is written --
     // what a path walk reads (merged layers and their parents, above the cutset layer kS)
-    // or, in an exact redo, the layers of the write mask; bit 29 (KEEP): the layer below is a
-    // merged layer and this one is not width-1, so its values of every batch cut go to bv.s2n
+    // or, in an exact redo, the layers of the write mask
     auto load_meta = [&](int kw) {
         const int k = kw + lane();
         const bool ok = k < d.T;
@@ -922,8 +920,7 @@ __device__ __forceinline__ void sweep_narrow(const NetDev &net, DD &d, BatchView
         m_noff = no;
         m_aoff = ao;
         const bool wrl = bv.wsel ? ((wsw >> (kk & 63)) & 1ull) != 0 : (k < kS && (kS >= d.T || ac != 0 || an != 0));
-        m_pk = (nn < 255u ? nn : 255u) | ((ac & 0xFFFu) << 8) | (wrl ? 0x40000000u : 0u) | (w ? 0x80000000u : 0u) |
-               (KEEP && bv.s2n && an != 0 && !w ? 0x20000000u : 0u);
+        m_pk = (nn < 255u ? nn : 255u) | ((ac & 0xFFFu) << 8) | (wrl ? 0x40000000u : 0u) | (w ? 0x80000000u : 0u);
         mmask = __ballot(ok && ac != 0);
     };
     auto rl = [](uint32_t v, int l) -> uint32_t { return (uint32_t)__builtin_amdgcn_readlane((int)v, l); };
@@ -989,8 +986,6 @@ __device__ __forceinline__ void sweep_narrow(const NetDev &net, DD &d, BatchView
             wrs[s] = ((rl(m_pk, lw + s) >> 30) & 1u) != 0;
         }
         const uint32_t nlast = rl(m_pk, lw + D - 1) & 255u;
-        // only the run's last layer can lie above a merged layer (a merged layer ends the run)
-        const bool kpl = KEEP && ((rl(m_pk, lw + D - 1) >> 29) & 1u) != 0;
         const bool wlane = c == nb - 1;   // the lane whose cut's state2 the path walks read
         auto items = [&](auto Uc, uint32_t base) {
             constexpr int U = decltype(Uc)::value;
@@ -1049,7 +1044,6 @@ __device__ __forceinline__ void sweep_narrow(const NetDev &net, DD &d, BatchView
                         for (int s = 0; s < D; s++)
                             if (wrs[s]) d.s2[nofs[s] + (wl[u][s] >> 16)] = xs[s];
                     }
-                    if (kpl) bv.s2n[(size_t)(nofs[D - 1] + (wl[u][D - 1] >> 16)) * CB + c] = xv;
                 }
             }
         };
@@ -1921,6 +1915,93 @@ __device__ __forceinline__ void cut_loop_single(const NetDev &net, DD &d, const 
     }
 }
 
+// Where the refold of narrow layer kp (not width-1) starts: the nearest layer above it that the
+// batch flagged width-1 (its summary sm holds the value every alive in-arc of the next layer
+// starts from), 0 for the root.  A merged layer has one node, so every layer in between is a
+// tree layer; -1 when one of them (or kp) has merged arcs after all.
+__device__ __forceinline__ int refold_start(const DD &d, const BatchView &bv, int kp) {
+    for (int hi = kp; hi >= 1; hi -= kWave) {
+        const int kk = hi - lane();   // lane 0 is the nearest layer
+        const bool w = kk >= 1 && bv.w1[kk] != 0;
+        const bool m = kk >= 1 && !w && d.acnt[kk] != 0;
+        const uint64_t bw = __ballot(w), bm = __ballot(m);
+        if (bw) {
+            const int j = (int)__ffsll((unsigned long long)bw) - 1;
+            return (bm & ((1ull << j) - 1ull)) ? -1 : hi - j;
+        }
+        if (bm) return -1;
+    }
+    return 0;
+}
+
+// Values of batch cut c (coefficient table ct, root value rv) of the tree layers ks + 1 .. kp,
+// all narrow, from the summary of the width-1 layer ks (see refold_start): nodes on lanes, layer
+// by layer, x = !in ? DMIN : (rank != 0 ? parent + coef : parent) -- the operations of fold_run
+// in its order, so the values are those the batch sweep had.  Layer j lands in the LDS value
+// buffer j & 1 (one value per node, stride 1) and its coefficients in bv.coef: both are free
+// during a redo, the restarted batch rewrites them.  The topology words and coefficients of
+// layer j + 1 load while layer j folds.
+// Inlined: as a noinline function it left k_relax<4> with more VGPR spills (29 against 25), see
+// DESIGN.md section 5; SGUFP_REFOLD_ATTR switches for that comparison.
+#ifndef SGUFP_REFOLD_ATTR
+#define SGUFP_REFOLD_ATTR __forceinline__
+#endif
+template <int CB>
+__device__ SGUFP_REFOLD_ATTR void refold_parent(const GBL uint16_t *tmir, const LDS uint32_t *noff, const LDS uint32_t *nn,
+                                                LDS double *vb, LDS double *coef, const GBL double *sm, GBL uint32_t *rstat,
+                                                const GBL double *ct, int g, int us, int c, double rv, int ks, int kp) {
+    constexpr int U = (kLdsBatchWidth + kWave - 1) / kWave;
+    uint32_t wa[U];
+    double ca;
+    auto load = [&](int j, uint32_t (&w)[U], double &cf) {
+        const uint32_t no = uni(noff[j]), n = uni(nn[j]);
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+            const uint32_t i = (uint32_t)(u * kWave + lane());
+            w[u] = (uint32_t)tmir[no + (i < n ? i : 0u)];
+        }
+        cf = ct[(size_t)(g + j - 1) * us + (lane() < us ? lane() : 0)];
+    };
+    const double x0 = ks == 0 ? rv : sm[(size_t)ks * CB + c];
+    load(ks + 1, wa, ca);
+    for (int j = ks + 1; j <= kp; j++) {
+        uint32_t wb[U] = {};
+        double cb = 0.0;
+        if (j < kp) load(j + 1, wb, cb);
+        sched_fence();
+        const LDS double *prev = vb + (size_t)((j - 1) & 1) * kLdsBatchWidth * CB;
+        LDS double *cur = vb + (size_t)(j & 1) * kLdsBatchWidth * CB;
+        LDS double *cfs = coef + (size_t)(j & 1) * us;
+        if (lane() < us) cfs[lane()] = ca;
+        wave_lds_sync();
+        const uint32_t n = uni(nn[j]);
+        double xp[U], cf[U];
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+            xp[u] = j == ks + 1 ? x0 : prev[mir_parent(wa[u])];
+            cf[u] = cfs[mir_rank(wa[u])];
+        }
+        sched_fence();
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+            const uint32_t i = (uint32_t)(u * kWave + lane());
+            const bool in = (wa[u] & kMirIn) != 0, reg = (wa[u] & (31u << kMirRankShift)) != 0;
+            if (i < n) cur[i] = !in ? DMIN : (reg ? xp[u] + cf[u] : xp[u]);
+        }
+        wave_lds_sync();
+#pragma unroll
+        for (int u = 0; u < U; u++) wa[u] = wb[u];
+        ca = cb;
+    }
+    if (rstat && lane() == 0) {
+        const uint32_t depth = (uint32_t)(kp - ks);
+        rstat[0] += 1u;
+        rstat[1] += depth;
+        if (depth > rstat[2]) rstat[2] = depth;
+        rstat[6 + min(depth, (uint32_t)(kRefoldStats - 7))] += 1u;
+    }
+}
+
 // Width-1 pruning of cut `id` over the layers of the fire mask fm (DD.cpp:3895-3928 /
 // 3987-4021): in each, every alive in-arc with parent.state2 + weight + gain <= thresh
 // goes, gain = maxState - state2 of the layer's single node.  Marks use the sweep's
@@ -1931,8 +2012,11 @@ __device__ __forceinline__ void cut_loop_single(const NetDev &net, DD &d, const 
 // BATCH: the state2 values are those the batch sweep computed for its cut c (root value rv).
 // The single node's is the layer's summary sm.  The layer above: a width-1 layer's only alive
 // node is the tail of every alive arc, and its value is that layer's summary (rv for the root);
-// a wide layer is in s2b; a narrow layer of several alive nodes lies above a merged layer and
-// was kept in s2n.  Otherwise the values are in d.s2, where the exact redo sweep wrote them.
+// a wide layer is in s2b; a narrow layer of several alive nodes lies above a merged layer, and
+// its values are folded again into LDS just before the layer is pruned (refold_parent: the
+// pruning of one layer edits nothing the refold of another reads -- arc flags, and the in-arc
+// flag of a width-1 layer's node, which a refold starts below).  Otherwise the values are in
+// d.s2, where the exact redo sweep wrote them.
 template <int CB, bool BATCH>
 __device__ __forceinline__ bool prune_layers(const NetDev &net, DD &d, const BatchView &bv, const Pool &pool, int id, int c,
                                              double rv, int first, int end, double maxState, double thresh) {
@@ -1940,6 +2024,7 @@ __device__ __forceinline__ bool prune_layers(const NetDev &net, DD &d, const Bat
     const int us = pool.ustride;
     const GBL double *ct = pool.coefT + (size_t)id * ((size_t)net.L * us);
     bool ok = true;
+    uint32_t nfold = 0;   // refolds of this redo (diagnostics)
     for (int wb = first & ~63; wb < end && ok; wb += kWave) {
         uint64_t b = bv.fm[wb >> 6];
         while (b && ok) {
@@ -1951,8 +2036,15 @@ __device__ __forceinline__ bool prune_layers(const NetDev &net, DD &d, const Bat
             const bool one = BATCH && (k == 1 || uni(bv.w1[k - 1]) != 0);
             const double ps1 = !one ? 0.0 : (k == 1 ? rv : bv.sm[(size_t)(k - 1) * CB + c]);
             const uint32_t ps = BATCH ? CB : 1;
-            const GBL double *pv = !BATCH ? d.s2 + pnoff
-                                   : (k - 1 >= d.kg ? bv.s2b + (size_t)(pnoff - bv.gbase) * CB : bv.s2n + (size_t)pnoff * CB) + c;
+            // a narrow parent layer of several alive nodes (redo_cut: only above a merged layer)
+            const bool fold = BATCH && !one && k - 1 < d.kg;
+            const GBL double *pv = !BATCH ? d.s2 + pnoff : bv.s2b + (fold ? (size_t)0 : (size_t)(pnoff - bv.gbase) * CB) + c;
+            const LDS double *lp = bv.vb + (size_t)((k - 1) & 1) * kLdsBatchWidth * CB;
+            if (fold) {
+                refold_parent<CB>(d.tmir, d.noff, d.nn, bv.vb, bv.coef, bv.sm, bv.rstat, ct, d.g, us, c, rv,
+                                  max(refold_start(d, bv, k - 1), 0), k - 1);
+                nfold++;
+            }
             uint32_t total = 0, pruned = 0;
             if (acnt) {
                 const uint32_t aoff = uni(d.aoff[k]);
@@ -1971,7 +2063,7 @@ __device__ __forceinline__ bool prune_layers(const NetDev &net, DD &d, const Bat
 #pragma unroll
                     for (int u = 0; u < U; u++) {
                         const uint32_t r = tp[u] >> kRankShift;
-                        px[u] = one ? ps1 : pv[(size_t)(tp[u] & kParentMask) * ps];
+                        px[u] = one ? ps1 : (fold ? lp[tp[u] & kMirParent] : pv[(size_t)(tp[u] & kParentMask) * ps]);
                         w[u] = r == 0 ? 0.0 : ck[r];
                     }
                     sched_fence();
@@ -2011,6 +2103,11 @@ __device__ __forceinline__ bool prune_layers(const NetDev &net, DD &d, const Bat
             if (total == pruned) ok = false;
         }
     }
+    if (BATCH && bv.rstat && nfold && lane() == 0) {
+        if (nfold > bv.rstat[3]) bv.rstat[3] = nfold;
+        if (first == 1) bv.rstat[4] += nfold;
+        bv.rstat[5] += 1u;
+    }
     wave_mem_sync();
     return ok;
 }
@@ -2044,22 +2141,24 @@ __device__ __forceinline__ bool fire_layers(const DD &d, BatchView &bv, int c, i
 // summaries of cut c.
 // unchanged (no edit since the batch sweep: same DD, same values): the batch sweep already
 // holds what the pruning reads -- the single nodes' values are the summaries, the layers
-// above them are in s2b or were kept in s2n -- so nothing is swept again.
-// Otherwise (an earlier cut of a feasibility batch removed leaves), or when the engine has
-// no s2n: a sweep with this cut alone that writes state2 of just those layers; the summaries
-// it recomputes must fire the same layers (checked; otherwise the sweep is repeated writing
-// every layer).  Returns false when a width-1 layer would lose all of its incoming arcs.
+// above them are width-1 themselves, in s2b, or a few tree layers below a width-1 summary
+// that prune_layers folds again -- so nothing is swept again.
+// Otherwise (an earlier cut of a feasibility batch removed leaves), or under
+// SGUFP_REDO_SWEEP=1: a sweep with this cut alone that writes state2 of just those layers; the
+// summaries it recomputes must fire the same layers (checked; otherwise the sweep is repeated
+// writing every layer).  Returns false when a width-1 layer would lose all of its incoming arcs.
 template <int CB>
-__device__ __forceinline__ bool redo_cut(const NetDev &net, DD &d, BatchView &bv, const Pool &pool, int c, int id,
+__device__ __forceinline__ bool redo_cut(const NetDev &net, DD &d, const Scratch &sc, BatchView &bv, const Pool &pool, int c, int id,
                                          double rv1, int first, int end, double thresh, double maxState,
                                          bool unchanged) {
     const int last = d.T - 1;
     const int nw = (d.T + 63) / 64;
     fire_layers<CB>(d, bv, c, first, end, thresh, maxState);
-    if (unchanged && bv.s2n) {
+    if (unchanged && !sc.redo_sweep) {
         // every firing layer must have the layer above it at hand (see prune_layers): a narrow
-        // layer of several alive nodes was kept only above a merged layer -- above a tree layer
-        // of one alive node there is none, the cascade leaves no childless parent
+        // layer of several alive nodes is folded again only above a merged layer -- above a tree
+        // layer of one alive node there is none, the cascade leaves no childless parent -- and
+        // only through tree layers (anything else means an edit nobody accounted for: sweep)
         bool have = true;
         for (int w = 0; w < nw; w++) {
             uint64_t b = bv.fm[w];
@@ -2067,6 +2166,7 @@ __device__ __forceinline__ bool redo_cut(const NetDev &net, DD &d, BatchView &bv
                 const int k = w * 64 + (int)(__ffsll((unsigned long long)b) - 1);
                 b &= b - 1;
                 have &= k == 1 || k - 1 >= d.kg || uni(bv.w1[k - 1]) != 0 || uni(d.acnt[k]) != 0;
+                if (have && k > 1 && k - 1 < d.kg && uni(bv.w1[k - 1]) == 0) have = refold_start(d, bv, k - 1) >= 0;
             }
         }
         if (have) {
@@ -2239,7 +2339,7 @@ __device__ __forceinline__ void cut_loop_batched(const NetDev &net, DD &d, const
         const double rv = root_fold_seq(pool, d, s, total);
         wave_lds_sync();
         st.stamp(4);
-        sweep_narrow<CB, true>(net, d, bv, pool, nb, rv, kS);
+        sweep_narrow<CB>(net, d, bv, pool, nb, rv, kS);
         st.stamp(1);
         if (d.kg == 0 && lane() < nb) bv.s2b[lane()] = rv;
         for (int k = max(d.kg, 1); k < last; k++) sweep_tail_layer<CB>(net, d, bv, pool, k, nb, kS);
@@ -2269,7 +2369,7 @@ __device__ __forceinline__ void cut_loop_batched(const NetDev &net, DD &d, const
                 if (rmc) { dd_cascade(d, (uint32_t)c + 1u); removed = true; }
                 if (!d.exact && dd_prune_check<CB>(d, bv, c, 1, last, -0.01, maxState)) {
                     st.stamp(4);
-                    if (!redo_cut<CB>(net, d, bv, pool, c, id, lane_get(rv, c), 1, last, -0.01, maxState, !removed)) {
+                    if (!redo_cut<CB>(net, d, sc, bv, pool, c, id, lane_get(rv, c), 1, last, -0.01, maxState, !removed)) {
                         st.status = kPrunedFeasibility;
                         return;
                     }
@@ -2324,7 +2424,7 @@ __device__ __forceinline__ void cut_loop_batched(const NetDev &net, DD &d, const
                 const int c = redo;
                 const int id = uni(bv.ids[c]);
                 double v = redo_v;
-                if (!redo_cut<CB>(net, d, bv, pool, c, id, lane_get(rv, c), 3, last - 1, incumbent - 0.01, redo_ms, true))
+                if (!redo_cut<CB>(net, d, sc, bv, pool, c, id, lane_get(rv, c), 3, last - 1, incumbent - 0.01, redo_ms, true))
                     v = DMIN;
                 st.applied++;
                 st.last_cut = id;
@@ -2351,6 +2451,7 @@ __global__ void __launch_bounds__(kWave, 2) k_relax(NetDev net, Scratch sc, Batc
     // the re-run after the cut-parallel phase of non-exact DDs: only the records it could
     // not settle (kNxFallback), in order, from scratch
     if (ex.redo && out.status[slot] != kNxFallback) return;
+    if (sc.rstat && lane() < kRefoldStats) sc.rstat[(size_t)slot * kRefoldStats + lane()] = 0;
 #ifdef SGUFP_PHASES
     const uint64_t t_start = wall_clock64();
 #endif
@@ -2424,7 +2525,7 @@ __global__ void __launch_bounds__(kWave, 2) k_relax(NetDev net, Scratch sc, Batc
         bv.sm = sc.sm + (size_t)slot * sc.Tcap * CB;
         bv.xm = sc.xm + (size_t)slot * sc.Tcap * CB;
         build_stream(d, n_merged, CB * pool.ustride);   // tmir_cap = Ncap + Acap >= Nn + Amir
-        bv.s2n = (sc.redo_sweep || d.Nn > (uint32_t)sc.nar_cap) ? nullptr : sc.s2n + (size_t)slot * sc.nar_cap * CB;
+        bv.rstat = sc.rstat ? sc.rstat + (size_t)slot * kRefoldStats : nullptr;
         const bool nxtry = ex.enabled && ex.nx && !ex.redo && !d.exact && pool.no >= ex.nx_min;
         if (d.stream) cut_loop_batched<CB>(net, d, sc, bv, pool, incumbent, st, efast, nxtry ? &ex : nullptr, slot, &nx_k0);
         else cut_loop_single(net, d, pool, incumbent, 0, st, efast);

@@ -1,6 +1,6 @@
 """Per-node diagnostics of one relaxation step on the bench workload (GPU).
 
-    python tools/relax_diag.py [--config C4 --seed 1 --nodes 4096 --cb 16]
+    python tools/relax_diag.py [--config C4 --seed 1 --nodes 4096 --cb 16 --refold]
 
 Prints the k_relax time, the distribution of per-wave wall-clock ticks against DD
 size / status / cuts applied / batched-sweep restarts."""
@@ -23,7 +23,10 @@ def main():
     ap.add_argument("--nodes", type=int, default=4096)
     ap.add_argument("--cb", default=None)
     ap.add_argument("--incumbent", default="p40")
+    ap.add_argument("--refold", action="store_true", help="also print the exact redos' refold counters")
     args = ap.parse_args()
+    if args.refold:
+        os.environ["SGUFP_REFOLD_STATS"] = "1"
     if args.cb:
         os.environ["SGUFP_CUT_BATCH"] = args.cb
     from sgufp_solver_amd import engine as E
@@ -77,6 +80,18 @@ def main():
     ph = eng.phases() / 100.0
     names = ["build", "narrow", "tail", "last", "post", "redo", "finish", "epilog"]
     print("phase us/node: " + ", ".join(f"{nm} {ph[:, k].mean():.0f}" for k, nm in enumerate(names)))
+    if args.refold:
+        # depth = tree layers folded again between the nearest width-1 summary and the parent
+        # layer of a firing merged layer (Engine.refold_stats)
+        rs = eng.refold_stats().astype(np.int64)
+        hist = rs[:, 6:].sum(0)
+        n_ref = int(rs[:, 0].sum())
+        p90 = int(np.searchsorted(np.cumsum(hist), 0.9 * n_ref)) if n_ref else 0
+        print(f"refolds per record: mean {rs[:, 0].mean():.2f} max {rs[:, 0].max()}; per redo with one "
+              f"{n_ref / max(1, rs[:, 5].sum()):.2f} (most {rs[:, 3].max()}); redos with a refold {rs[:, 5].sum()} of {redo.sum()}; "
+              f"in feasibility batches {rs[:, 4].sum()}")
+        print(f"refold depth (layers): mean {rs[:, 1].sum() / max(1, n_ref):.2f} p90 {p90}{'+' if p90 >= 9 else ''} "
+              f"max {rs[:, 2].max()}; layers refolded per record {rs[:, 1].mean():.1f}; histogram 0..9+ {hist.tolist()}")
     big = np.argsort(-us)[:5]
     for k in big:
         print(f"  slow node {k}: {us[k]:.0f} us, dd {dn[k]} nodes, {dl[k]} layers, sweeps {sw[k]}, status {st[k]}, "
