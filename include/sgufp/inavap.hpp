@@ -166,6 +166,10 @@ class GuroSolver {
   public:
     explicit GuroSolver(const std::shared_ptr<Network> &networkPtr);
     std::pair<CutType, Inavap::Cut> solveSubProblem(const std::vector<int16_t> &path);
+    // an extension (the reference keeps the cut only): the path's optimal flow per network arc
+    // in every scenario, [S][m]; zeros for a scenario that is not optimal (its status as
+    // sgufp_subproblem_detail through *status)
+    std::vector<std::vector<int16_t>> solveFlows(const std::vector<int16_t> &path, std::vector<int32_t> *status = nullptr);
 };
 
 class NodeExplorer {
@@ -218,6 +222,16 @@ class DDSolver {
     bool complete = false;                           // the last search emptied every frontier
     int64_t maxRounds = 0;                           // stop after this many rounds (0: none)
     double heuristicIncumbent = DOUBLE_MIN;          // the seed's value (DOUBLE_MIN: none)
+    // what the last search leaves besides its value (extensions: the reference prints the value
+    // only): the routing the value belongs to -- one decision per DD layer, as solveSubProblem
+    // takes it; empty when no leaf beat the seeded value -- the bound max(value, largest ub on
+    // any shard's open frontier), the open records with ub > value over all shards, and
+    // (bestBound - value) / max(1, |value|): 0 when complete, inf without an incumbent
+    std::vector<int16_t> bestPath;
+    double value = DOUBLE_MIN;
+    double bestBound = DOUBLE_MAX;
+    int64_t openNodes = 0;
+    double gap() const;
     int64_t received = 0;   // records this shard got through work sharing
     // counters of the last solve (SOLVER_COUNTERS, DDSolver.h:380-392)
     sgufp_bnb_stats totals{};

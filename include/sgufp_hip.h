@@ -212,6 +212,17 @@ int sgufp_subproblem_warm(sgufp_ctx *ctx, int n, const int64_t *path_off, const 
  * shortest-path solve (warm: of the repair; a warm start that fell back to a cold solve
  * reports -1 - cold augmentations) and Bellman-Ford passes. */
 int sgufp_subproblem_stats(sgufp_ctx *ctx, int32_t *augmentations, int32_t *passes);
+/* The recourse flows of n paths (an extension: the reference's subproblem keeps the cut only and
+ * has no counterpart).  Per (path, scenario) [n * S]: status as sgufp_subproblem_detail, objective,
+ * flow_reward = sum_a reward_a * x_a of the exported flow; flows [n * S * m] int16 per network arc
+ * (zeros where status != 0); mean_flow [n * m] = (double)(sum_s x) / S for paths whose S scenarios
+ * are all optimal, zeros otherwise.  Any output pointer may be NULL.  The scenarios are solved
+ * cold by the warm-start kernels, which store their optimal flows in a buffer this call owns:
+ * it touches neither the pools nor the warm ring (the per-scenario detail of the last call,
+ * sgufp_subproblem_detail / _stats, is this call's last chunk of paths afterwards).  Networks of
+ * more than 2046 nodes return SGUFP_ERR_CAPACITY and launch nothing. */
+int sgufp_subproblem_flows(sgufp_ctx *ctx, int n, const int64_t *path_off, const int16_t *paths, int32_t *status,
+                           double *objective, double *flow_reward, int16_t *flows, double *mean_flow);
 /* Inavap::getKey(q, i, j) (Cut.h:342-344) of every coefficient slot (n_slots entries). */
 int sgufp_slot_keys(const sgufp_ctx *ctx, uint64_t *keys);
 /* Append cuts given as dense rows (n_slots + 1 doubles each, as sgufp_subproblem returns
@@ -290,6 +301,24 @@ int sgufp_bnb_set_limits(sgufp_ctx *ctx, int max_refine_iters, double round_seco
 int sgufp_bnb_set_trace(sgufp_ctx *ctx, int enabled);
 int sgufp_bnb_trace(sgufp_ctx *ctx, int kind, int64_t *count, int64_t *path_entries, int32_t *record, int32_t *code,
                     int32_t *row, double *value, int64_t *path_off, int16_t *paths);
+/* -- the incumbent's routing and the proven bound (extensions: the reference has no counterpart,
+ *    it keeps and prints the incumbent's value only) --
+ * The context stores one solution: value and argmax path (one int16 decision per DD layer, as
+ * sgufp_subproblem takes them) of the closed exact leaf that last raised *incumbent in a
+ * sgufp_bnb_step of this context -- the first such leaf in batch order when several reach the
+ * round's maximum -- or what sgufp_incumbent_set / sgufp_incumbent_sync installed.  The path is
+ * copied on the device in the round that improves; no other round pays for it.
+ * sgufp_frontier_clear drops the stored solution.  *len = 0 and *value = DOUBLE_MIN (the lowest
+ * double) when none; path holds up to totalLayers entries; any output pointer may be NULL. */
+int sgufp_bnb_incumbent(sgufp_ctx *ctx, double *value, int16_t *path /* [total_layers] */, int32_t *len);
+int sgufp_incumbent_set(sgufp_ctx *ctx, double value, const int16_t *path, int32_t len);   /* len <= total_layers */
+/* Over the stack: *open = records with ub > incumbent (those sgufp_bnb_step would not prune by
+ * bound, DDSolver.cpp:707-711), *max_ub = the largest such ub (DOUBLE_MIN when *open == 0).
+ * Between rounds max(incumbent, *max_ub) bounds the optimum from above: every open subtree is on
+ * the stack, deferred records included, with the bound their loop reached.  One grid-stride
+ * kernel over the records' ub (nothing is launched for an empty stack); deterministic. */
+int sgufp_frontier_bound(sgufp_ctx *ctx, double incumbent, double *max_ub, int64_t *open);
+
 /* Read back pool cuts [first, first + count) of one list (insertion order) as dense rows,
  * e.g. to all-gather the cuts a round produced to the other frontier shards. */
 int sgufp_cuts_rows(sgufp_ctx *ctx, int is_feasibility, int first, int count, double *rhs, double *rows);
@@ -318,6 +347,11 @@ int sgufp_comm_init_loopback(sgufp_ctx *ctx, sgufp_loopback *group, int rank);
 void sgufp_comm_destroy(sgufp_ctx *ctx);
 /* *inout := max over the shards (replaces the CAS-max, DDSolver.cpp:723-731). */
 int sgufp_incumbent_allreduce(sgufp_ctx *ctx, double *inout);
+/* Shards (an extension, see sgufp_bnb_incumbent): after sgufp_incumbent_allreduce gave z, every
+ * shard ends up holding the path of the lowest rank whose stored value == z; if no shard holds z
+ * (a seed nobody beat) every shard ends with none.  One fixed-size block per shard through the
+ * byte all-gather.  One shard: only drops a stored value != z. */
+int sgufp_incumbent_sync(sgufp_ctx *ctx, double z);
 /* Every shard's pool rows appended since the last exchange are appended on every other
  * shard, in rank order, feasibility list then optimality list (Container::add of another
  * worker's cut).  *received = rows this shard appended. */

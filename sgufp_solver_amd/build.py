@@ -10,6 +10,7 @@
     libsgufp_host.so  C++ mirror of the reference's host API (Network / NodeExplorer /
                       GuroSolver / DDSolver, include/sgufp/inavap.hpp) on top of the C ABI
     host_api_test     C++ driver of that API (tests/host/host_api_test.cpp)
+    solution_test     C++ driver of the solver's routing / bound / flows (tests/host/solution_test.cpp)
 """
 from __future__ import annotations
 
@@ -100,13 +101,14 @@ def build_native(force: bool = False, verbose: bool = False) -> str:
             cxx = shutil.which("g++") or "g++"
             _run([cxx, "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", f"-I{os.path.join(ROOT, 'include')}",
                   *host_srcs, "-o", hlib, f"-L{LIBDIR}", "-lsgufp_hip", "-Wl,-rpath,$ORIGIN"])
-        # C++ driver of the host API used by tests/test_host_api.py
-        tsrc = os.path.join(ROOT, "tests", "host", "host_api_test.cpp")
-        texe = os.path.join(LIBDIR, "host_api_test")
-        if os.path.exists(tsrc) and (force or _stale(texe, [tsrc, hlib] + hheaders)):
-            cxx = shutil.which("g++") or "g++"
-            _run([cxx, "-O2", "-std=c++17", "-Wall", f"-I{os.path.join(ROOT, 'include')}", tsrc, "-o", texe,
-                  f"-L{LIBDIR}", "-lsgufp_host", "-lsgufp_hip", "-Wl,-rpath,$ORIGIN"])
+        # C++ drivers of the host API used by tests/test_host_api.py and tests/test_solution_host.py
+        for name in ("host_api_test", "solution_test"):
+            tsrc = os.path.join(ROOT, "tests", "host", name + ".cpp")
+            texe = os.path.join(LIBDIR, name)
+            if os.path.exists(tsrc) and (force or _stale(texe, [tsrc, hlib] + hheaders)):
+                cxx = shutil.which("g++") or "g++"
+                _run([cxx, "-O2", "-std=c++17", "-Wall", f"-I{os.path.join(ROOT, 'include')}", tsrc, "-o", texe,
+                      f"-L{LIBDIR}", "-lsgufp_host", "-lsgufp_hip", "-Wl,-rpath,$ORIGIN"])
     return lib
 
 

@@ -42,7 +42,24 @@ hipError_t launch_append_cuts(const int32_t *cut_type, const double *cut_rhs, co
                               int us, double *row_ub, int32_t *row_id, uint8_t *is_feas, hipStream_t st);
 hipError_t launch_gather_rows(const double *rows, const double *rhs, const int32_t *ids, int k, int stride, double *out,
                               hipStream_t st);
+hipError_t launch_frontier_bound(const double *ub, int64_t n, double z, double *pmax, int64_t *pcnt, int *blocks,
+                                 hipStream_t st);
 }  // namespace sgufp
+
+bool sgufp_ctx::inc_store(double value, const int16_t *src, int32_t len, hipMemcpyKind kind) {
+    const size_t cap = (size_t)std::max(std::max(sc.Lcap, net.L), 1);
+    if (len < 0 || (size_t)len > cap) {
+        err = "incumbent path longer than totalLayers";
+        return false;
+    }
+    if (!d_inc_path && !alloc(d_inc_path, cap, "incumbent path")) return false;
+    if (len && !hip_ok(hipMemcpyAsync(d_inc_path, src, (size_t)len * sizeof(int16_t), kind, stream), "incumbent path"))
+        return false;
+    inc_value = value;
+    inc_len = len;
+    inc_host_valid = false;
+    return true;
+}
 
 void sgufp_ctx::decode_states(const uint16_t *gl, const uint32_t *mask, size_t count, int64_t *states_off,
                               int16_t *states) const {
@@ -283,6 +300,7 @@ int sgufp_frontier_clear(sgufp_ctx *ctx) {
     ctx->fr_n = 0;
     ctx->fr_sol_top = 0;
     ctx->deferred_seen.clear();
+    ctx->inc_drop();
     if (ctx->seen.paths) {   // a new search starts with small seen-path lists again
         if (!ctx->sync()) return SGUFP_ERR_HIP;
         ctx->release(ctx->seen.paths);
@@ -417,6 +435,55 @@ int sgufp_cuts_rows(sgufp_ctx *ctx, int is_feasibility, int first, int count, do
         if (rhs) rhs[c] = buf[(size_t)c * blk];
         if (rows) std::memcpy(rows + (size_t)c * stride, &buf[(size_t)c * blk + 1], stride * sizeof(double));
     }
+    return SGUFP_OK;
+}
+
+int sgufp_bnb_incumbent(sgufp_ctx *ctx, double *value, int16_t *path, int32_t *len) {
+    if (!ctx) return SGUFP_ERR_ARG;
+    if (path && ctx->inc_len && !ctx->inc_host_valid) {
+        ctx->inc_host.resize((size_t)ctx->inc_len);
+        if (!ctx->download(ctx->inc_host.data(), ctx->d_inc_path, (size_t)ctx->inc_len) || !ctx->sync())
+            return SGUFP_ERR_HIP;
+        ctx->inc_host_valid = true;
+    }
+    if (value) *value = ctx->inc_value;
+    if (len) *len = ctx->inc_len;
+    if (path && ctx->inc_len) std::memcpy(path, ctx->inc_host.data(), (size_t)ctx->inc_len * sizeof(int16_t));
+    return SGUFP_OK;
+}
+
+int sgufp_incumbent_set(sgufp_ctx *ctx, double value, const int16_t *path, int32_t len) {
+    if (!ctx || len < 0 || len > ctx->net.L || (len && !path)) return SGUFP_ERR_ARG;
+    if (!ctx->inc_store(value, path, len, hipMemcpyHostToDevice) || !ctx->sync()) return SGUFP_ERR_HIP;
+    ctx->inc_host.assign(path, path + len);
+    ctx->inc_host_valid = true;
+    return SGUFP_OK;
+}
+
+int sgufp_frontier_bound(sgufp_ctx *ctx, double incumbent, double *max_ub, int64_t *open) {
+    if (!ctx) return SGUFP_ERR_ARG;
+    double mx = -__DBL_MAX__;
+    int64_t cnt = 0;
+    if (ctx->fr_n > 0) {   // an empty stack launches nothing
+        if (!ctx->d_fb_max &&
+            (!ctx->alloc(ctx->d_fb_max, kBoundBlocks, "frontier bound") || !ctx->alloc(ctx->d_fb_cnt, kBoundBlocks, "frontier bound")))
+            return SGUFP_ERR_HIP;
+        int g = 0;
+        if (!ctx->hip_ok(launch_frontier_bound(ctx->fr.ub, ctx->fr_n, incumbent, ctx->d_fb_max, ctx->d_fb_cnt, &g, ctx->stream),
+                         "k_frontier_bound"))
+            return SGUFP_ERR_HIP;
+        std::vector<double> pm((size_t)g);
+        std::vector<int64_t> pc((size_t)g);
+        if (!ctx->download(pm.data(), ctx->d_fb_max, (size_t)g) || !ctx->download(pc.data(), ctx->d_fb_cnt, (size_t)g) ||
+            !ctx->sync())
+            return SGUFP_ERR_HIP;
+        for (int i = 0; i < g; i++) {
+            mx = std::max(mx, pm[i]);
+            cnt += pc[i];
+        }
+    }
+    if (max_ub) *max_ub = mx;
+    if (open) *open = cnt;
     return SGUFP_OK;
 }
 
@@ -771,10 +838,21 @@ struct BnbRound {
     // ---- 5: incumbent (DDSolver.cpp:723-731) ----
     int update_incumbent() {
         znew = z;
+        int best = -1;   // the first slot in batch order that reaches the maximum (strict >)
         for (int k = 0; k < b; k++)
-            if (lbv[k] > znew) znew = lbv[k];
+            if (lbv[k] > znew) {
+                znew = lbv[k];
+                best = k;
+            }
         S.improved = znew > z ? 1 : 0;
         incumbent = znew;
+        if (best < 0) return SGUFP_OK;
+        // the stored solution: that leaf's argmax path, copied on the device before the
+        // children overwrite anything (only an improving round pays the length's round trip)
+        uint16_t len = 0;
+        if (!c.download(&len, o.path_len + best, 1) || !c.sync() ||
+            !c.inc_store(znew, o.path + (size_t)best * c.sc.Lcap, (int32_t)len, hipMemcpyDeviceToDevice))
+            return SGUFP_ERR_HIP;
         return SGUFP_OK;
     }
 

@@ -11,6 +11,8 @@
 // int16 solution spans, so the HBM traffic is the bytes moved.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+
 #include "dd_device.hpp"
 #include "wave.hpp"
 
@@ -140,6 +142,41 @@ hipError_t launch_append_rows(const double *src, int n, int stride, int first, d
     if (n <= 0) return hipSuccess;
     hipLaunchKernelGGL(k_append_rows, dim3(n), dim3(256), 0, st, src, n, stride, first, rows, rhs, coefT, slot_tab, L,
                        us, row_ub);
+    return hipGetLastError();
+}
+
+// Global bound over the open frontier (an extension: the reference computes none): of the
+// stack's ub[0 .. n), the records a round would not prune by bound (ub > z, DDSolver.cpp:707-711)
+// are counted and their largest ub kept.  Grid-stride, one wave per block, one {max, count}
+// partial per block; the host finishes over the partials.  An f64 max and an integer count do
+// not depend on the order, so the result is the same for any grid.
+__global__ void __launch_bounds__(kWave) k_frontier_bound(const double *ub, int64_t n, double z, double *pmax,
+                                                          int64_t *pcnt) {
+    double mx = -__DBL_MAX__;
+    int64_t cnt = 0;
+    for (int64_t i = (int64_t)blockIdx.x * kWave + lane(); i < n; i += (int64_t)gridDim.x * kWave) {
+        const double u = ub[i];
+        if (u > z) {
+            cnt++;
+            mx = smax(mx, u);
+        }
+    }
+    mx = lane_reduce<1>(mx, [](double a, double b) { return smax(a, b); });
+    cnt = lane_reduce<1>(cnt, [](int64_t a, int64_t b) { return a + b; });
+    if (lane() == 0) {
+        pmax[blockIdx.x] = mx;
+        pcnt[blockIdx.x] = cnt;
+    }
+}
+
+// blocks <= kBoundBlocks partials are written; returns the number of blocks through *blocks
+hipError_t launch_frontier_bound(const double *ub, int64_t n, double z, double *pmax, int64_t *pcnt, int *blocks,
+                                 hipStream_t st) {
+    *blocks = 0;
+    if (n <= 0) return hipSuccess;
+    const int g = (int)std::min<int64_t>((n + kWave - 1) / kWave, kBoundBlocks);
+    hipLaunchKernelGGL(k_frontier_bound, dim3(g), dim3(kWave), 0, st, ub, n, z, pmax, pcnt);
+    *blocks = g;
     return hipGetLastError();
 }
 

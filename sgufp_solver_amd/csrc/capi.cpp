@@ -985,6 +985,26 @@ int sgufp_subproblem_stats(sgufp_ctx *ctx, int32_t *augmentations, int32_t *pass
     return SGUFP_OK;
 }
 
+// chains of a path = m minus its matched out-arcs (distinct valid decisions); the LDS
+// holds the most any path of the batch needs (a wave that finds more flags an error)
+static int chain_cap(int m, int n, const int64_t *path_off, const int16_t *paths) {
+    std::vector<uint8_t> used((size_t)m, 0);
+    int cap = 0;
+    for (int k = 0; k < n; k++) {
+        int matched = 0;
+        for (int64_t i = path_off[k]; i < path_off[k + 1]; i++) {
+            const int d = paths[i];
+            if (d >= 0 && d < m && !used[d]) { used[d] = 1; matched++; }
+        }
+        for (int64_t i = path_off[k]; i < path_off[k + 1]; i++) {
+            const int d = paths[i];
+            if (d >= 0 && d < m) used[d] = 0;
+        }
+        cap = std::max(cap, m - matched);
+    }
+    return std::max(cap, 1);
+}
+
 static int subproblem_run(sgufp_ctx *ctx, int n, const int64_t *path_off, const int16_t *paths, const int32_t *src,
                           const int32_t *dst, int32_t *type, double *rhs, double *rows, double *obj_mean) {
     if (!ctx || n < 0 || (n && (!path_off || !paths))) return SGUFP_ERR_ARG;
@@ -1002,26 +1022,7 @@ static int subproblem_run(sgufp_ctx *ctx, int n, const int64_t *path_off, const 
         return SGUFP_ERR_HIP;
     SubIO io = ctx->sio;
     io.n_paths = n;
-    // chains of a path = m minus its matched out-arcs (distinct valid decisions); the LDS
-    // holds the most any path of the batch needs (a wave that finds more flags an error)
-    {
-        const int m = ctx->net.m;
-        std::vector<uint8_t> used((size_t)m, 0);
-        int cap = 0;
-        for (int k = 0; k < n; k++) {
-            int matched = 0;
-            for (int64_t i = path_off[k]; i < path_off[k + 1]; i++) {
-                const int d = paths[i];
-                if (d >= 0 && d < m && !used[d]) { used[d] = 1; matched++; }
-            }
-            for (int64_t i = path_off[k]; i < path_off[k + 1]; i++) {
-                const int d = paths[i];
-                if (d >= 0 && d < m) used[d] = 0;
-            }
-            cap = std::max(cap, m - matched);
-        }
-        io.nct_cap = std::max(cap, 1);
-    }
+    io.nct_cap = chain_cap(ctx->net.m, n, path_off, paths);
     io.path_off = ctx->d_spoff;
     io.paths = ctx->d_spaths;
     io.path_slot = nullptr;
@@ -1053,6 +1054,89 @@ int sgufp_subproblem_detail(sgufp_ctx *ctx, int32_t *status, double *objective, 
         (dual_objective && !ctx->download(dual_objective, ctx->sio.dual, cnt)) || !ctx->sync())
         return SGUFP_ERR_HIP;
     return SGUFP_OK;
+}
+
+// An extension (the reference's subproblem returns the cut only): the WARM kernels run cold
+// (every source -1) and store path k's flows in slot k of an export buffer this call owns -- the
+// layout of the warm ring, which is neither reserved nor touched -- in chunks of paths that keep
+// the buffer under kFlowBytes.
+int sgufp_subproblem_flows(sgufp_ctx *ctx, int n, const int64_t *path_off, const int16_t *paths, int32_t *status,
+                           double *objective, double *flow_reward, int16_t *flows, double *mean_flow) {
+    if (!ctx || n < 0 || (n && (!path_off || !paths))) return SGUFP_ERR_ARG;
+    if (n == 0) return SGUFP_OK;
+    for (int k = 0; k < n; k++)
+        if (path_off[k + 1] < path_off[k] || path_off[k + 1] - path_off[k] > ctx->net.L) {
+            ctx->err = "path longer than totalLayers";
+            return SGUFP_ERR_ARG;
+        }
+    if (ctx->net.n + 2 > 32 * 64) {   // the WARM layout's node masks (warm_reserve)
+        ctx->err = "subproblem flows need n + 2 <= 2048 network nodes";
+        return SGUFP_ERR_CAPACITY;
+    }
+    if (!ctx->sub_init()) return SGUFP_ERR_HIP;
+    constexpr size_t kFlowBytes = (size_t)256 << 20;
+    const size_t S = (size_t)ctx->net.S, m = (size_t)ctx->net.m, nn = (size_t)ctx->net.n;
+    const size_t per = S * (m * sizeof(int16_t) + nn * sizeof(int32_t) + 1);
+    const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)n, kFlowBytes / std::max<size_t>(per, 1)));
+    int16_t *ex = nullptr;
+    int32_t *ea = nullptr, *esrc = nullptr, *edst = nullptr;
+    uint8_t *eok = nullptr;
+    double *erew = nullptr, *emean = nullptr;
+    std::vector<int32_t> src((size_t)chunk, -1), dst((size_t)chunk);
+    for (int k = 0; k < chunk; k++) dst[(size_t)k] = k;
+    int rc = SGUFP_OK;
+    if (!ctx->alloc(ex, (size_t)chunk * S * m, "flow export") || !ctx->alloc(ea, (size_t)chunk * S * nn, "flow export") ||
+        !ctx->alloc(eok, (size_t)chunk * S, "flow export") || !ctx->alloc(esrc, (size_t)chunk, "flow export") ||
+        !ctx->alloc(edst, (size_t)chunk, "flow export") || !ctx->alloc(erew, (size_t)chunk * S, "flow export") ||
+        !ctx->alloc(emean, (size_t)chunk * m, "flow export") || !ctx->upload(esrc, src.data(), src.size()) ||
+        !ctx->upload(edst, dst.data(), dst.size()))
+        rc = SGUFP_ERR_HIP;
+    for (int k0 = 0; k0 < n && rc == SGUFP_OK; k0 += chunk) {
+        const int c = std::min(chunk, n - k0);
+        const int64_t *po = path_off + k0;
+        const size_t total = (size_t)(po[c] - po[0]);
+        std::vector<int64_t> off(po, po + c + 1);
+        for (auto &o : off) o -= po[0];
+        // the kernel writes a slot only for optimal scenarios: zeros everywhere else
+        if (!ctx->sub_grow(c, std::max<size_t>(total, 1)) || !ctx->upload(ctx->d_spoff, off.data(), off.size()) ||
+            !ctx->upload(ctx->d_spaths, paths + po[0], total) ||
+            !ctx->hip_ok(hipMemsetAsync(ex, 0, (size_t)c * S * m * sizeof(int16_t), ctx->stream), "memset") ||
+            !ctx->hip_ok(hipMemsetAsync(ea, 0, (size_t)c * S * nn * sizeof(int32_t), ctx->stream), "memset") ||
+            !ctx->hip_ok(hipMemsetAsync(eok, 0, (size_t)c * S, ctx->stream), "memset")) {
+            rc = SGUFP_ERR_HIP;
+            break;
+        }
+        SubIO io = ctx->sio;
+        io.n_paths = c;
+        io.nct_cap = chain_cap(ctx->net.m, c, po, paths);
+        io.path_off = ctx->d_spoff;
+        io.paths = ctx->d_spaths;
+        io.path_slot = nullptr;
+        io.path_len = nullptr;
+        io.path_stride = 0;
+        io.warm_src = esrc;
+        io.warm_dst = edst;
+        io.wst_x = ex;
+        io.wst_a = ea;
+        io.wst_ok = eok;
+        if (!ctx->hip_ok(launch_subproblem(ctx->sn, io, ctx->stream), "subproblem launch") ||
+            !ctx->hip_ok(launch_flow_summary(c, (int)S, (int)m, ctx->sn.reward, ex, eok, erew, emean, ctx->stream),
+                         "k_flow_summary")) {
+            rc = SGUFP_ERR_HIP;
+            break;
+        }
+        ctx->sub_last_n = c;
+        const size_t cs = (size_t)c * S, b0 = (size_t)k0 * S;
+        if ((status && !ctx->download(status + b0, io.status, cs)) || (objective && !ctx->download(objective + b0, io.obj, cs)) ||
+            (flow_reward && !ctx->download(flow_reward + b0, erew, cs)) ||
+            (flows && !ctx->download(flows + b0 * m, ex, cs * m)) ||
+            (mean_flow && !ctx->download(mean_flow + (size_t)k0 * m, emean, (size_t)c * m)) || !ctx->sync())
+            rc = SGUFP_ERR_HIP;
+    }
+    if (rc != SGUFP_OK) (void)ctx->sync();   // nothing of the call is in flight when its buffers go
+    ctx->release(ex); ctx->release(ea); ctx->release(eok); ctx->release(esrc); ctx->release(edst);
+    ctx->release(erew); ctx->release(emean);
+    return rc;
 }
 
 int sgufp_cuts_clear(sgufp_ctx *ctx) {

@@ -27,6 +27,8 @@ size_t relax_lds_bytes(int Tcap, int Lcap, int cb, int us);
 size_t sub_lds_bytes(int n, int m, int nct_cap, int nz, int nw, int kbytes = 8, bool warm = false);
 hipError_t launch_subproblem(const SubNet &N, const SubIO &io, hipStream_t st);
 hipError_t launch_warm_pick(const SubIO &io, const WarmRing &wr, int ptr, hipStream_t st);
+hipError_t launch_flow_summary(int P, int S, int m, const int32_t *reward, int16_t *x, const uint8_t *ok,
+                               double *flow_reward, double *mean_flow, hipStream_t st);
 hipError_t launch_relax(const NetDev &, const Scratch &, const BatchIn &, const Pool &, const BatchOut &, double, int,
                         const ExactIO &, int, hipStream_t);
 // exact_kernels.hip
@@ -151,6 +153,21 @@ struct sgufp_ctx {
     bool loop_reserve(int slots, int cap);
     bool seen_upload(int slot, const std::vector<std::vector<int16_t>> &paths);
     bool seen_download(int slot, int count, std::vector<std::vector<int16_t>> &paths);
+    // the stored solution (an extension: the reference keeps the incumbent's value only): the
+    // argmax path of the closed exact leaf that last raised the incumbent in a sgufp_bnb_step,
+    // or what sgufp_incumbent_set / sgufp_incumbent_sync installed.  The path stays on the
+    // device; the host mirror is filled when a caller asks for it.
+    double inc_value = -__DBL_MAX__;          // DOUBLE_MIN: none
+    int32_t inc_len = 0;
+    int16_t *d_inc_path = nullptr;            // [Lcap]
+    std::vector<int16_t> inc_host;
+    bool inc_host_valid = false;
+    bool inc_store(double value, const int16_t *src, int32_t len, hipMemcpyKind kind);   // queued on the stream
+    void inc_drop() { inc_value = -__DBL_MAX__; inc_len = 0; inc_host_valid = false; }
+    // sgufp_frontier_bound: per-block partials of k_frontier_bound
+    double *d_fb_max = nullptr;
+    int64_t *d_fb_cnt = nullptr;
+    uint8_t *d_inc_blk = nullptr;             // sgufp_incumbent_sync: [(world + 1) blocks of {value, len, path[Lcap]}]
     int bnb_max_iters = 0;                    // refinement iterations per round (0: no limit)
     int64_t chunk_lps = 32768;                // scenario LPs per refinement iteration under a round
                                               // deadline (SGUFP_CHUNK_LPS)

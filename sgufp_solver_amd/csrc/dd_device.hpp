@@ -20,6 +20,7 @@ namespace sgufp {
 constexpr int kWave = 64;          // one DD per 64-lane wavefront (one single-wave workgroup)
 constexpr int kMaxU = 32;          // state universe <= 32 -> u32 masks
 constexpr int kLdsWidth = 512;     // layers up to this width keep their state2 in LDS during a sweep
+constexpr int kBoundBlocks = 1024; // blocks (partials) of k_frontier_bound at most
 
 // per-node result status (Inavap::OutObject::STATUS_OP, NodeExplorer.h:81-85, plus extensions)
 enum NodeStatus : int32_t {

@@ -4,7 +4,9 @@
 
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <ctime>
+#include <limits>
 #include <sstream>
 #include <vector>
 #include <cstdio>
@@ -164,6 +166,23 @@ std::pair<CutType, Cut> GuroSolver::solveSubProblem(const std::vector<int16_t> &
     return {type == 1 ? FEASIBILITY : OPTIMALITY, Cut{rhs, std::move(coeff)}};
 }
 
+std::vector<std::vector<int16_t>> GuroSolver::solveFlows(const std::vector<int16_t> &path, std::vector<int32_t> *status) {
+    sgufp_network_info info{};
+    dev.check(sgufp_get_network_info(dev.get(), &info), "network info");
+    const size_t S = (size_t)info.scenarios, m = (size_t)info.m;
+    int64_t off[2] = {0, (int64_t)path.size()};
+    static const int16_t empty = 0;
+    std::vector<int32_t> st(S);
+    std::vector<int16_t> x(S * m);
+    dev.check(sgufp_subproblem_flows(dev.get(), 1, off, path.empty() ? &empty : path.data(), st.data(), nullptr, nullptr,
+                                     x.data(), nullptr),
+              "subproblem flows");
+    std::vector<std::vector<int16_t>> out(S);
+    for (size_t s = 0; s < S; s++) out[s].assign(x.begin() + (long)(s * m), x.begin() + (long)((s + 1) * m));
+    if (status) *status = st;
+    return out;
+}
+
 // ---- NodeExplorer --------------------------------------------------------------------------
 NodeExplorer::NodeExplorer(const std::shared_ptr<Network> &networkPtr_)
     : networkPtr{networkPtr_}, dev{*networkPtr_, 1}, solver{networkPtr_} {}
@@ -305,7 +324,13 @@ double DDSolver::restricted_incumbent(double z) {
         Path path((size_t)poff[1]);
         dev.check(sgufp_restricted_paths(g, poff, path.empty() ? nullptr : path.data()), "restricted paths");
         if (have && path == prev) {
-            if (rlb == prev_lb) return std::max(z, rlb);             // {lowerBound, ...}
+            if (rlb == prev_lb) {                                    // {lowerBound, ...}
+                // the seed's routing is the stored solution until a leaf beats it
+                if (rlb > z)
+                    dev.check(sgufp_incumbent_set(g, rlb, path.empty() ? nullptr : path.data(), (int32_t)path.size()),
+                              "incumbent set");
+                return std::max(z, rlb);
+            }
         }
         prev = path;
         prev_lb = rlb;
@@ -415,7 +440,36 @@ double DDSolver::startSolver(double known_optimal) {
         received += got;
         if (st.exact > 0 || got > 0) diving = false;
     }
+    // what the search leaves besides its value (extensions of the reference): the routing of
+    // the final z -- the lowest shard holding it -- and the bound over every shard's open frontier
+    dev.check(sgufp_incumbent_sync(g, z), "incumbent sync");
+    sgufp_network_info info{};
+    dev.check(sgufp_get_network_info(g, &info), "network info");
+    bestPath.assign((size_t)std::max(info.total_layers, 1), 0);
+    double v = DOUBLE_MIN;
+    int32_t len = 0;
+    dev.check(sgufp_bnb_incumbent(g, &v, bestPath.data(), &len), "incumbent path");
+    bestPath.resize(v == z ? (size_t)len : 0);
+    double mx = DOUBLE_MIN;
+    int64_t open = 0;
+    dev.check(sgufp_frontier_bound(g, z, &mx, &open), "frontier bound");
+    if (world > 1) {
+        dev.check(sgufp_incumbent_allreduce(g, &mx), "bound all-reduce");
+        std::vector<int64_t> all((size_t)world);
+        dev.check(sgufp_comm_allgather_i64(g, &open, 1, all.data()), "open all-gather");
+        open = 0;
+        for (int64_t o : all) open += o;
+    }
+    value = z;
+    bestBound = std::max(z, mx);
+    openNodes = open;
     return z;
+}
+
+double DDSolver::gap() const {
+    if (complete) return 0.0;
+    if (value == DOUBLE_MIN) return std::numeric_limits<double>::infinity();
+    return (bestBound - value) / std::max(1.0, std::fabs(value));
 }
 
 std::string DDSolver::workerStats() const {

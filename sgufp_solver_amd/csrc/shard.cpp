@@ -354,6 +354,57 @@ int sgufp_incumbent_allreduce(sgufp_ctx *ctx, double *inout) {
     return SGUFP_OK;
 }
 
+// An extension (the reference keeps the incumbent's value only): one fixed-size block
+// {f64 value, i32 len, i32 pad, int16 path[cap]} per shard through the byte all-gather; the
+// lowest rank whose stored value is z owns the solution and every shard installs its path.
+int sgufp_incumbent_sync(sgufp_ctx *ctx, double z) {
+    if (!ctx) return SGUFP_ERR_ARG;
+    if (!ctx->comm) {   // one shard
+        if (ctx->inc_value != z) ctx->inc_drop();
+        return SGUFP_OK;
+    }
+    const int W = ctx->world, me = ctx->rank;
+    const size_t cap = (size_t)std::max(std::max(ctx->sc.Lcap, ctx->net.L), 1);
+    const size_t blk = (16 + cap * sizeof(int16_t) + 7) / 8 * 8;
+    if (!ctx->d_inc_blk && !ctx->alloc(ctx->d_inc_blk, blk * (size_t)(W + 1), "incumbent sync")) return SGUFP_ERR_HIP;
+    uint8_t *send = ctx->d_inc_blk + blk * (size_t)W;
+    uint8_t hdr[16] = {};
+    const int32_t len = ctx->inc_len;
+    std::memcpy(hdr, &ctx->inc_value, 8);
+    std::memcpy(hdr + 8, &len, 4);
+    std::vector<uint8_t> all(blk * (size_t)W);
+    if (!ctx->hip_ok(hipMemsetAsync(send, 0, blk, ctx->stream), "memset") || !ctx->upload(send, hdr, sizeof hdr) ||
+        (len && !ctx->hip_ok(hipMemcpyAsync(send + 16, ctx->d_inc_path, (size_t)len * sizeof(int16_t),
+                                            hipMemcpyDeviceToDevice, ctx->stream), "D2D")) ||
+        !ctx->comm->allgather(ctx, send, ctx->d_inc_blk, blk) || !ctx->download(all.data(), ctx->d_inc_blk, all.size()) ||
+        !ctx->sync())
+        return SGUFP_ERR_HIP;
+    int owner = -1;
+    int32_t olen = 0;
+    for (int r = 0; r < W && owner < 0; r++) {
+        double v;
+        std::memcpy(&v, &all[blk * (size_t)r], 8);
+        std::memcpy(&olen, &all[blk * (size_t)r + 8], 4);
+        if (v == z) owner = r;
+    }
+    if (owner < 0) {   // a seed nobody beat
+        ctx->inc_drop();
+        return SGUFP_OK;
+    }
+    if (owner == me) return SGUFP_OK;
+    if (olen < 0 || (size_t)olen > cap) {
+        ctx->err = "incumbent sync: bad path length received";
+        return SGUFP_ERR_STATE;
+    }
+    if (!ctx->inc_store(z, (const int16_t *)(ctx->d_inc_blk + blk * (size_t)owner + 16), olen, hipMemcpyDeviceToDevice) ||
+        !ctx->sync())
+        return SGUFP_ERR_HIP;
+    const int16_t *hp = (const int16_t *)&all[blk * (size_t)owner + 16];
+    ctx->inc_host.assign(hp, hp + olen);
+    ctx->inc_host_valid = true;
+    return SGUFP_OK;
+}
+
 // [world][k] int64 all-gather of k values per shard (k <= 4)
 static bool allgather_i64(sgufp_ctx *ctx, const int64_t *mine, int k, std::vector<int64_t> &all) {
     const int W = ctx->world;

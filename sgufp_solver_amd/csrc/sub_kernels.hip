@@ -1744,6 +1744,53 @@ hipError_t launch_warm_pick(const SubIO &io, const WarmRing &wr, int ptr, hipStr
 }
 
 // ---------------------------------------------------------------------------------------
+// Summary of exported flows (sgufp_subproblem_flows): x [P][S][m] int16 as the WARM kernels store
+// them, ok [P][S] (the scenario was optimal and stored its flows).  Blocks [0, P * S): one wave
+// per (path, scenario) sums reward[a] * x[a] in int64 (coalesced over arcs, wave reduce) and
+// zeroes the flows of a scenario that is not ok (one that turned into an error after its store).
+// Blocks from P * S on: one thread per (path, arc) sums x over the scenarios (coalesced across
+// arcs) for paths whose S scenarios are all ok -- the integer sum is divided once by S -- and
+// writes 0 otherwise; these threads read ok and the flows of all-ok paths only, which the first
+// blocks do not write.
+__global__ void __launch_bounds__(kWave) k_flow_summary(int P, int S, int m, const int32_t *reward, int16_t *x,
+                                                        const uint8_t *ok, double *flow_reward, double *mean_flow) {
+    const int t = (int)threadIdx.x;
+    const int nps = P * S;
+    if ((int)blockIdx.x < nps) {
+        const size_t b = blockIdx.x;
+        int16_t *xb = x + b * (size_t)m;
+        int64_t sum = 0;
+        if (ok[b]) {
+            for (int a = t; a < m; a += kWave) sum += (int64_t)reward[a] * (int64_t)xb[a];
+        } else {
+            for (int a = t; a < m; a += kWave) xb[a] = 0;
+        }
+        for (int o = kWave / 2; o > 0; o >>= 1) sum += (int64_t)__shfl_xor((long long)sum, o, kWave);
+        if (t == 0) flow_reward[b] = (double)sum;
+        return;
+    }
+    const int per = (m + kWave - 1) / kWave;   // arc blocks per path
+    const int r = (int)blockIdx.x - nps;
+    const int p = r / per;
+    const int a = (r - p * per) * kWave + t;
+    if (p >= P || a >= m) return;
+    bool all = true;
+    for (int s = 0; s < S; s++) all = all && ok[(size_t)p * S + s];
+    int64_t sum = 0;
+    if (all)
+        for (int s = 0; s < S; s++) sum += (int64_t)x[((size_t)p * S + s) * m + a];
+    mean_flow[(size_t)p * m + a] = all ? (double)sum / (double)S : 0.0;
+}
+
+hipError_t launch_flow_summary(int P, int S, int m, const int32_t *reward, int16_t *x, const uint8_t *ok,
+                               double *flow_reward, double *mean_flow, hipStream_t st) {
+    if (P <= 0 || S <= 0 || m <= 0) return hipSuccess;
+    const unsigned blocks = (unsigned)P * (unsigned)S + (unsigned)P * (unsigned)((m + kWave - 1) / kWave);
+    hipLaunchKernelGGL(k_flow_summary, dim3(blocks), dim3(kWave), 0, st, P, S, m, reward, x, ok, flow_reward, mean_flow);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------
 size_t sub_lds_bytes(int n, int m, int nct_cap, int nz, int nw, int kbytes, bool warm) {
     size_t off[kSubLdsParts];
     return sub_lds_layout(n, m, nct_cap, nz, nw, off, kbytes, warm);

@@ -12,7 +12,7 @@ from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from .pools import NodeRecord, PoolCut, RelaxResult
+from .pools import DOUBLE_MIN, NodeRecord, PoolCut, RelaxResult
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SGUFP_LIB_PATH") or os.path.join(HERE, "lib", "libsgufp_hip.so")
@@ -40,6 +40,7 @@ EXPORTS = [
     "sgufp_dd_build", "sgufp_dd_apply", "sgufp_dd_solution", "sgufp_dd_cutset",
     "sgufp_loopback_create", "sgufp_loopback_destroy", "sgufp_comm_init_loopback",
     "sgufp_subproblem_warm", "sgufp_subproblem_stats",
+    "sgufp_subproblem_flows", "sgufp_bnb_incumbent", "sgufp_incumbent_set", "sgufp_incumbent_sync", "sgufp_frontier_bound",
 ]
 
 
@@ -168,6 +169,11 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     lib.sgufp_loopback_destroy.restype = None
     lib.sgufp_loopback_destroy.argtypes = [P]
     lib.sgufp_comm_init_loopback.argtypes = [P, P, C.c_int]
+    lib.sgufp_subproblem_flows.argtypes = [P, C.c_int, P, P, P, P, P, P, P]
+    lib.sgufp_bnb_incumbent.argtypes = [P, P, P, P]
+    lib.sgufp_incumbent_set.argtypes = [P, C.c_double, P, C.c_int32]
+    lib.sgufp_incumbent_sync.argtypes = [P, C.c_double]
+    lib.sgufp_frontier_bound.argtypes = [P, C.c_double, P, P]
     lib.sgufp_dd_build.argtypes = [P]
     lib.sgufp_dd_apply.argtypes = [P, C.c_int, C.c_int, C.c_double, C.c_int64, P, P, C.c_double, P]
     lib.sgufp_dd_solution.argtypes = [P, C.c_int, P, P]
@@ -565,6 +571,31 @@ class Engine:
                                                        _ptr(typ), _ptr(rhs), _ptr(rows), _ptr(obj)))
         return typ[:n], rhs[:n], rows[:n], obj[:n]
 
+    def subproblem_flows(self, paths: Sequence[Sequence[int]]):
+        """The recourse flows of each path (sgufp_subproblem_flows; an extension of the reference).
+
+        Returns (status[n, S], objective[n, S], flow_reward[n, S], flows[n, S, m] int16,
+        mean_flow[n, m]): status as subproblem_detail, flows zero where status != 0, mean_flow
+        the scenario mean for paths whose scenarios are all optimal (zeros otherwise).  Leaves
+        the pools and the warm ring as they are."""
+        n = len(paths)
+        S, m = self.info.scenarios, self.info.m
+        off = np.zeros(n + 1, dtype=np.int64)
+        for k, p in enumerate(paths):
+            off[k + 1] = off[k] + len(p)
+        flat = np.concatenate([np.asarray(p, dtype=np.int16) for p in paths]) if n else np.zeros(1, np.int16)
+        if flat.size == 0:
+            flat = np.zeros(1, np.int16)
+        st = np.zeros(max(n * S, 1), dtype=np.int32)
+        ob = np.zeros(max(n * S, 1), dtype=np.float64)
+        fr = np.zeros(max(n * S, 1), dtype=np.float64)
+        x = np.zeros(max(n * S * m, 1), dtype=np.int16)
+        mean = np.zeros(max(n * m, 1), dtype=np.float64)
+        self._check(self.lib.sgufp_subproblem_flows(self.ctx, n, _ptr(off), _ptr(flat), _ptr(st), _ptr(ob), _ptr(fr),
+                                                    _ptr(x), _ptr(mean)))
+        return (st[:n * S].reshape(n, S), ob[:n * S].reshape(n, S), fr[:n * S].reshape(n, S),
+                x[:n * S * m].reshape(n, S, m), mean[:n * m].reshape(n, m))
+
     def subproblem_stats(self, n: int):
         """Per (path, scenario) of the last call: augmenting paths (negative: a warm start fell
         back cold) and Bellman-Ford passes, each [n, S]."""
@@ -655,6 +686,34 @@ class Engine:
         """Bound the refinement loops of one bnb_step (0: no limit); unfinished exact
         records go back on top of the frontier."""
         self._check(self.lib.sgufp_bnb_set_limits(self.ctx, int(max_refine_iters), C.c_double(round_seconds)))
+
+    # -- the incumbent's routing and the bound over the frontier (extensions of the reference) --
+    def bnb_incumbent(self) -> Tuple[float, Optional[List[int]]]:
+        """(value, path) of the stored solution (sgufp_bnb_incumbent): the closed exact leaf that
+        last raised the incumbent in a bnb_step, or what incumbent_set / incumbent_sync installed;
+        (DOUBLE_MIN, None) when none."""
+        v, n = C.c_double(0.0), C.c_int32(0)
+        buf = np.zeros(max(self.info.total_layers, 1), dtype=np.int16)
+        self._check(self.lib.sgufp_bnb_incumbent(self.ctx, C.byref(v), _ptr(buf), C.byref(n)))
+        if n.value == 0 and v.value == DOUBLE_MIN:
+            return v.value, None
+        return v.value, [int(x) for x in buf[:n.value]]
+
+    def incumbent_set(self, value: float, path: Sequence[int]):
+        p = np.asarray(list(path), dtype=np.int16)
+        self._check(self.lib.sgufp_incumbent_set(self.ctx, C.c_double(value), _ptr(p) if p.size else None, int(p.size)))
+
+    def incumbent_sync(self, z: float):
+        """Shards: every shard ends with the path of the lowest rank whose stored value == z
+        (none when no shard holds z); one shard: drops a stored value != z."""
+        self._check(self.lib.sgufp_incumbent_sync(self.ctx, C.c_double(z)))
+
+    def frontier_bound(self, incumbent: float) -> Tuple[float, int]:
+        """(max_ub, open) over the stack: the records with ub > incumbent and their largest ub
+        (DOUBLE_MIN when none); max(incumbent, max_ub) bounds the optimum from above."""
+        mx, cnt = C.c_double(0.0), C.c_int64(0)
+        self._check(self.lib.sgufp_frontier_bound(self.ctx, C.c_double(incumbent), C.byref(mx), C.byref(cnt)))
+        return mx.value, cnt.value
 
     def bnb_set_trace(self, on: bool = True):
         """Keep what each bnb_step round did (sgufp_bnb_set_trace) for bnb_trace()."""

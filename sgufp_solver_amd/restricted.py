@@ -85,8 +85,13 @@ class RestrictedExplorer:
 
     def incumbent(self, records: Sequence[NodeRecord], optimal_lb: float = DOUBLE_MIN) -> float:
         """The best converged bound of the records (optimal_lb when none converges)."""
-        best = optimal_lb
+        return self.incumbent_path(records, optimal_lb)[0]
+
+    def incumbent_path(self, records: Sequence[NodeRecord], optimal_lb: float = DOUBLE_MIN):
+        """incumbent() with the routing it belongs to: (value, path of the first record that
+        reaches it; None when no record converges above optimal_lb)."""
+        best, path = optimal_lb, None
         for r in self.explore(records, optimal_lb):
             if r.converged and r.lb > best:
-                best = r.lb
-        return best
+                best, path = r.lb, list(r.path)
+        return best, path

@@ -90,6 +90,15 @@ class DDSolver:
         self.seconds = 0.0
         self.shard_comm = None
         self.received = 0
+        # what the search leaves besides its value (extensions of the reference, see result()):
+        # the incumbent's routing -- engines with bnb_incumbent -- and the bound over the open
+        # frontier -- engines with frontier_bound
+        self.network_path = network_path
+        self.value = DOUBLE_MIN
+        self.best_value = DOUBLE_MIN
+        self.best_path = None
+        self.best_bound = None
+        self.open_nodes = None
 
     # -- collectives ---------------------------------------------------------------
     def _comm(self):
@@ -122,10 +131,18 @@ class DDSolver:
         # rows already shared: the heuristic's cuts below are new, so the first exchange
         # sends them to every shard (the global pool, DDSolver.h:415-416)
         marks = {1: eng.cuts_count(1), 0: eng.cuts_count(0)}
+        has_inc = hasattr(eng, "bnb_incumbent")
+        self.value = self.best_value = DOUBLE_MIN
+        self.best_path = self.best_bound = self.open_nodes = None
         if self.restricted_width > 0 and rank == 0:
             from .restricted import RestrictedExplorer
-            h = RestrictedExplorer(eng, self.restricted_width).incumbent([NodeRecord(0, DOUBLE_MIN, DOUBLE_MAX, [], [])], z)
+            h, hp = RestrictedExplorer(eng, self.restricted_width).incumbent_path(
+                [NodeRecord(0, DOUBLE_MIN, DOUBLE_MAX, [], [])], z)
             self.heuristic_incumbent = h
+            if has_inc and hp is not None:   # the seed's routing counts as a stored solution
+                self.best_value, self.best_path = h, hp
+                if hasattr(eng, "incumbent_set"):
+                    eng.incumbent_set(h, hp)
             z = max(z, h)
         keys = ("popped", "relaxed", "pruned_bound", "pruned_feasibility", "pruned_optimality", "exact",
                 "exact_closed", "subproblems", "new_feasibility_cuts", "new_optimality_cuts", "children", "pushed",
@@ -150,7 +167,10 @@ class DDSolver:
                 if self.time_budget > 0:
                     secs = max(1e-3, min(left, secs) if secs > 0 else left)
                 eng.bnb_set_limits(self.round_iters, secs)
+            z_round = z
             z, st = eng.bnb_step(z, batch)
+            if has_inc and z > z_round:   # the round improved: its leaf's routing
+                self.best_value, self.best_path = eng.bnb_incumbent()
             if diving and int(getattr(st, "exact", 0) if not isinstance(st, dict) else st["exact"]) > 0:
                 diving = False   # the dive reached exact leaves: cuts exist from here on
             self.rounds += 1
@@ -193,7 +213,71 @@ class DDSolver:
             if g[:, 1].any():
                 break
             self.received += comm.rebalance(eng, sizes)
+        self._finish(z, comm)
         return z
+
+    def _finish(self, z: float, comm):
+        """After the last round (complete or stopped): one exchange fixes which shard's routing
+        belongs to the final z (the lowest rank holding it), one gives the bound over every
+        shard's open frontier.  Engines without bnb_incumbent / frontier_bound skip theirs."""
+        eng = self.eng
+        self.value = z
+        if hasattr(eng, "bnb_incumbent"):
+            if self.native_world:
+                eng.incumbent_sync(z)
+                v, p = eng.bnb_incumbent()
+                self.best_path = p if v == z else None
+            elif comm is None:
+                if self.best_value != z:
+                    self.best_path = None   # a seed nobody beat
+                if hasattr(eng, "incumbent_sync"):
+                    eng.incumbent_sync(z)
+            else:
+                mine = self.best_path is not None and self.best_value == z
+                blob = np.concatenate([np.array([z], dtype=np.float64).view(np.uint8),
+                                       np.asarray(self.best_path, dtype=np.int16).view(np.uint8)]) \
+                    if mine else np.zeros(0, np.uint8)
+                self.best_path = None
+                for r, b in enumerate(comm.allgather_bytes(blob)):
+                    if b.size >= 8 and float(np.ascontiguousarray(b[:8]).view(np.float64)[0]) == z:
+                        self.best_path = [int(x) for x in np.ascontiguousarray(b[8:]).view(np.int16)]
+                        if r != comm.rank and hasattr(eng, "incumbent_set"):
+                            eng.incumbent_set(z, self.best_path)
+                        break
+            self.best_value = z
+        if hasattr(eng, "frontier_bound"):
+            mx, op = eng.frontier_bound(z)
+            if self.native_world:
+                mx = eng.incumbent_allreduce(mx)
+                op = int(eng.comm_allgather_i64([int(op)], self.native_world)[:, 0].sum())
+            elif comm is not None:
+                mx = comm.allreduce_max(mx)
+                op = int(comm.allgather_i64([int(op)])[:, 0].sum())
+            self.best_bound = max(z, mx)
+            self.open_nodes = int(op)
+
+    @property
+    def gap(self):
+        """(best_bound - value) / max(1, |value|): 0 for a completed search, inf without an
+        incumbent, None when the engine gives no bound."""
+        from .solution import gap_of
+        return gap_of(self.value, self.best_bound, self.complete)
+
+    def result(self):
+        """The value with its routing, the proven bound and the gap (solution.Solution)."""
+        from .solution import Solution, arcs_of_file, matching_of_path
+        matching = None
+        if self.best_path is not None and self.network_path and hasattr(self.eng, "processing_order"):
+            tails, heads = arcs_of_file(self.network_path)
+            matching = matching_of_path(self.eng.processing_order()[0], tails, heads, self.best_path)
+        return Solution(self.value, None if self.best_path is None else list(self.best_path), matching,
+                        self.best_bound, self.gap, self.open_nodes, self.complete)
+
+    def flows(self):
+        """Per-scenario arc flows of the best routing (Engine.subproblem_flows on its path)."""
+        if self.best_path is None:
+            raise RuntimeError("DDSolver.flows: no routing is known")
+        return self.eng.subproblem_flows([self.best_path])
 
     def start(self, known_opt: float, solver_counters: bool = False):
         """DDSolver::start (DDSolver.cpp:848-867): solve, time, print the reference's line
