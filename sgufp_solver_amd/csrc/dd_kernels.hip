@@ -891,20 +891,35 @@ __device__ __forceinline__ void sweep_narrow(const NetDev &net, DD &d, BatchView
     if (d.ng == 0) return;
     double pf[PC] = {};
     uint32_t pt[PT] = {};
-    auto commit = [&](int slot) {
-        LDS double *ring = bv.cring + (size_t)slot * kStageEntries;
-        LDS uint16_t *tr = bv.tring + (size_t)slot * kTopoEntries;
-#pragma unroll
-        for (int jj = 0; jj < PC; jj++) ring[lane() + jj * kWave] = pf[jj];
-#pragma unroll
-        for (int jj = 0; jj < PT; jj++) tr[lane() + jj * kWave] = (uint16_t)pt[jj];
-    };
     // Per-group layer metadata in registers: lane l <-> layer k0 + l of the current staging
     // group (and the layers after it): node offset, merged-arc offset and a packed word
     // nn:8 | acnt:12 | w1 (bit 31), read per layer with v_readlane instead of a serialised
     // LDS round trip per field; mmask: which of those layers are merged layers.
     uint32_t m_noff = 0, m_aoff = 0, m_pk = 0;
     uint64_t mmask = 0;
+    // ring entry e = lane + jj * 64 of a group stages the coefficient of layer k0 + lo, batch
+    // cut cc, rank r: the per-lane constants are computed once per sweep (c_lo: lo in the low
+    // byte; above it the bit of commit's group mask that tells a rank 0 of a tree layer: lo
+    // when r == 0, else 31)
+    int c_lo[PC];
+    uint32_t c_off[PC];
+    // gw: the group's first layer in the metadata window.  Rank 0 (the decision -1) of a tree
+    // layer is staged as -0.0: x + -0.0 is x bit for bit for every x, both zeros included, so
+    // fold_run adds the staged coefficient without asking for the rank.  Merged layers keep
+    // the table's +0.0 (their width-1 summary is defined as parent + 0.0).
+    auto commit = [&](int slot, int gw) {
+        LDS double *ring = bv.cring + (size_t)slot * kStageEntries;
+        LDS uint16_t *tr = bv.tring + (size_t)slot * kTopoEntries;
+        // merged layers of the group (at most kStageLayers); bit 31 stands for "not rank 0"
+        const uint32_t gm = (uint32_t)(mmask >> gw) | 0x80000000u;
+#pragma unroll
+        for (int jj = 0; jj < PC; jj++) {
+            const bool tree0 = ((gm >> (c_lo[jj] >> 8)) & 1u) == 0;
+            ring[lane() + jj * kWave] = tree0 ? -0.0 : pf[jj];
+        }
+#pragma unroll
+        for (int jj = 0; jj < PT; jj++) tr[lane() + jj * kWave] = (uint16_t)pt[jj];
+    };
     // bit 30 of the packed word: this layer's state2 (of the last batch cut) is written --
     // what a path walk reads (merged layers and their parents, above the cutset layer kS)
     // or, in an exact redo, the layers of the write mask
@@ -925,16 +940,12 @@ __device__ __forceinline__ void sweep_narrow(const NetDev &net, DD &d, BatchView
     };
     auto rl = [](uint32_t v, int l) -> uint32_t { return (uint32_t)__builtin_amdgcn_readlane((int)v, l); };
 
-    // ring entry e = lane + jj * 64 of a group stages the coefficient of layer k0 + lo, batch
-    // cut cc, rank r: the per-lane constants are computed once per sweep
-    int c_lo[PC];
-    uint32_t c_off[PC];
 #pragma unroll
     for (int jj = 0; jj < PC; jj++) {
         const int e = lane() + jj * kWave;
         const int lo = e / per_layer, rem = e - lo * per_layer;
         const int cc = rem / us, r = rem - cc * us;
-        c_lo[jj] = lo;
+        c_lo[jj] = lo | ((r == 0 && lo < 31 ? lo : 31) << 8);
         c_off[jj] = (uint32_t)(bv.ids[cc < nb ? cc : 0] * (int)ltab + r);
     }
     // prefetch of the group [k0g, k1g) into registers (layer offsets from the metadata
@@ -945,7 +956,7 @@ __device__ __forceinline__ void sweep_narrow(const NetDev &net, DD &d, BatchView
         // entries past the group load the group's last layer again (never read): no branch
 #pragma unroll
         for (int jj = 0; jj < PC; jj++) {
-            const int k = min(k0g + c_lo[jj], k1g - 1);
+            const int k = min(k0g + (c_lo[jj] & 255), k1g - 1);
             pf[jj] = pool.coefT[(size_t)c_off[jj] + (size_t)(uint32_t)((d.g + k - 1) * us)];
         }
 #pragma unroll
@@ -978,12 +989,14 @@ __device__ __forceinline__ void sweep_narrow(const NetDev &net, DD &d, BatchView
         const int l0 = ka - k0_, lw = ka - kw_;   // ring / metadata-window positions
         uint32_t ebase[D], nofs[D];
         bool w1s[D], wrs[D];
+        bool outs = false;   // some layer of the run has a summary or a walk value to store
 #pragma unroll
         for (int s = 0; s < D; s++) {
             nofs[s] = rl(m_noff, lw + s);
             ebase[s] = nofs[s] - gn0_;
             w1s[s] = (rl(m_pk, lw + s) >> 31) != 0;
             wrs[s] = ((rl(m_pk, lw + s) >> 30) & 1u) != 0;
+            outs |= w1s[s] | wrs[s];
         }
         const uint32_t nlast = rl(m_pk, lw + D - 1) & 255u;
         const bool wlane = c == nb - 1;   // the lane whose cut's state2 the path walks read
@@ -993,7 +1006,7 @@ __device__ __forceinline__ void sweep_narrow(const NetDev &net, DD &d, BatchView
 #pragma unroll
             for (int u = 0; u < U; u++) {
                 const uint32_t i = base + (uint32_t)(u * G + grp);
-                cur[u] = i < nlast ? i : nlast - 1u;
+                cur[u] = min(i, nlast - 1u);
             }
 #pragma unroll
             for (int s = D - 1; s >= 0; s--) {
@@ -1018,25 +1031,25 @@ __device__ __forceinline__ void sweep_narrow(const NetDev &net, DD &d, BatchView
             sched_fence();
 #pragma unroll
             for (int u = 0; u < U; u++) {
-                const bool alive = (wl[u][D - 1] & kMirAlive) != 0;
-                double xv = x[u], xs[D], xms[D];
+                double xv = x[u], xs[D];
+                // rank 0 is staged as -0.0 (commit): the add stands for reg ? x + coef : x
 #pragma unroll
                 for (int s = 0; s < D; s++) {
-                    const uint32_t w = wl[u][s];
-                    const bool in = (w & kMirIn) != 0, reg = (w & (31u << kMirRankShift)) != 0;
-                    const double xn = !in ? DMIN : (reg ? xv + cf[u][s] : xv);
-                    xms[s] = !in ? DMAX : (reg ? xn : xv + 0.0);
-                    xs[s] = xv = xn;
+                    const bool in = (wl[u][s] & kMirIn) != 0;
+                    xs[s] = xv = in ? xv + cf[u][s] : DMIN;
                 }
                 ob[(wl[u][D - 1] >> 16) * CB + c] = xv;
-                // the summaries / walk values of the run's layers: one divergent branch per
-                // item (the per-layer conditions are wave-uniform)
-                if (alive && cv) {
+                // the summaries / walk values of the run's layers: one wave-uniform test, then
+                // one divergent branch per item (the per-layer conditions are wave-uniform)
+                if (outs && (wl[u][D - 1] & kMirAlive) != 0 && cv) {
 #pragma unroll
                     for (int s = 0; s < D; s++) {
                         if (w1s[s]) {
+                            const uint32_t w = wl[u][s];
+                            const bool in = (w & kMirIn) != 0, reg = (w & (31u << kMirRankShift)) != 0;
+                            const double xp = s ? xs[s ? s - 1 : 0] : x[u];
                             bv.sm[(size_t)(ka + s) * CB + c] = xs[s];
-                            bv.xm[(size_t)(ka + s) * CB + c] = xms[s];
+                            bv.xm[(size_t)(ka + s) * CB + c] = !in ? DMAX : (reg ? xs[s] : xp + 0.0);
                         }
                     }
                     if (wlane) {
@@ -1060,7 +1073,7 @@ __device__ __forceinline__ void sweep_narrow(const NetDev &net, DD &d, BatchView
     int kw = k0;
     load_meta(kw);
     issue(k0, k1, kw);
-    commit(0);
+    commit(0, 0);
     if (d.ng > 1) issue(k1, uni((int)d.gstart[2]), kw);
     uint32_t gn0 = rl(m_noff, 0), gnN = rl(m_noff, k1 - kw) - gn0, ga0 = rl(m_aoff, 0);
     wave_lds_sync();
@@ -1070,7 +1083,7 @@ __device__ __forceinline__ void sweep_narrow(const NetDev &net, DD &d, BatchView
             // next group: its words and coefficients were issued one group ago
             j++;
             slot ^= 1;
-            commit(slot);
+            commit(slot, k1 - kw);   // before the window moves
             k0 = k1;
             k1 = uni((int)d.gstart[j + 1]);
             const int k2 = j + 1 < d.ng ? uni((int)d.gstart[j + 2]) : k1;
@@ -1134,7 +1147,7 @@ __device__ __forceinline__ void sweep_narrow(const NetDev &net, DD &d, BatchView
                 for (int u = 0; u < U; u++) {
                     if (CLAMP) {
                         const uint32_t a = base + (uint32_t)(u * G + grp);
-                        wd[u] = word(ebase + (a < alast ? a : alast));
+                        wd[u] = word(ebase + min(a, alast));
                     } else {
                         wd[u] = (uint32_t)tw[u * G];
                     }
