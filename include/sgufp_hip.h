@@ -160,6 +160,9 @@ int sgufp_dd_cutset(sgufp_ctx *ctx, int node, double ub, int64_t *n_children);
 int sgufp_batch_debug(sgufp_ctx *ctx, int64_t *ticks, int32_t *redo);
 /* ticks per phase [n * 8]: build, narrow sweep, tail layers, last layer, replay/post, redo, finish, tail */
 int sgufp_batch_phases(sgufp_ctx *ctx, int64_t *phase);
+/* the narrow-sweep phase of the batch sweeps split [n * 3]: merged layers, staging-group switches (with
+ * the sweep's set-up), folded tree runs; zeros from the production library */
+int sgufp_batch_narrow_split(sgufp_ctx *ctx, int64_t *split);
 /* Refolds of the exact redos in the last relax (a context created under SGUFP_REFOLD_STATS=1,
  * else SGUFP_ERR_STATE), [n * 16] per node: 0 refolds (a narrow layer above a firing merged layer
  * folded again from the nearest width-1 summary), 1 layers refolded, 2 the deepest refold, 3 the

@@ -158,7 +158,7 @@ bool sgufp_ctx::init() {
         !alloc(out.ub, B, "out") || !alloc(out.nchild, B, "out") || !alloc(out.sol_need, B, "out") ||
         !alloc(out.dd_nodes, B, "out") || !alloc(out.dd_arcs, B, "out") || !alloc(out.dd_layers, B, "out") ||
         !alloc(out.sweeps, B, "out") || !alloc(out.path, B * sc.Lcap, "out") || !alloc(out.path_len, B, "out") ||
-        !alloc(out.ticks, B, "out") || !alloc(out.redo, B, "out") || !alloc(out.phase, B * 8, "out"))
+        !alloc(out.ticks, B, "out") || !alloc(out.redo, B, "out") || !alloc(out.phase, B * kPhaseSlots, "out"))
         return false;
     // batch input
     if (!alloc(d_gl, B, "batch") || !alloc(d_sollen, B, "batch") || !alloc(d_lb, B, "batch") ||
@@ -1411,9 +1411,23 @@ int sgufp_batch_phases(sgufp_ctx *ctx, int64_t *phase) {
         std::fill(phase, phase + (size_t)ctx->n * 8, (int64_t)0);
         return SGUFP_OK;
     }
-    std::vector<uint64_t> t((size_t)ctx->n * 8);
+    std::vector<uint64_t> t((size_t)ctx->n * kPhaseSlots);
     if (!ctx->download(t.data(), ctx->out.phase, t.size()) || !ctx->sync()) return SGUFP_ERR_HIP;
-    for (size_t k = 0; k < t.size(); k++) phase[k] = (int64_t)t[k];
+    for (size_t i = 0; i < (size_t)ctx->n; i++)
+        for (int k = 0; k < 8; k++) phase[i * 8 + k] = (int64_t)t[i * kPhaseSlots + k];
+    return SGUFP_OK;
+}
+
+int sgufp_batch_narrow_split(sgufp_ctx *ctx, int64_t *split) {
+    if (!ctx || !ctx->relaxed || !split) return ctx ? SGUFP_ERR_STATE : SGUFP_ERR_ARG;
+    if (!relax_has_phases()) {
+        std::fill(split, split + (size_t)ctx->n * 3, (int64_t)0);
+        return SGUFP_OK;
+    }
+    std::vector<uint64_t> t((size_t)ctx->n * kPhaseSlots);
+    if (!ctx->download(t.data(), ctx->out.phase, t.size()) || !ctx->sync()) return SGUFP_ERR_HIP;
+    for (size_t i = 0; i < (size_t)ctx->n; i++)
+        for (int k = 0; k < 3; k++) split[i * 3 + k] = (int64_t)t[i * kPhaseSlots + 8 + k];
     return SGUFP_OK;
 }
 

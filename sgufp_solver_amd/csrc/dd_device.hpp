@@ -163,9 +163,13 @@ struct BatchOut {
     int16_t SGUFP_GBL *path;             // [max_batch * Lcap] argmax path of exact DDs
     uint16_t SGUFP_GBL *path_len;
     uint64_t SGUFP_GBL *ticks;           // wall_clock64 ticks (100 MHz) spent by each node's wave
-    uint64_t SGUFP_GBL *phase;           // [max_batch * 8] ticks per phase: build, narrow, tail, last, post, redo, finish
+    uint64_t SGUFP_GBL *phase;           // [max_batch * kPhaseSlots] ticks per phase: build, narrow, tail, last, post, redo,
+                                         // finish, epilogue; then the narrow phase's split: merged layers, group
+                                         // switches, folded tree runs
     uint32_t SGUFP_GBL *redo;            // batched sweeps restarted after an exact single-cut redo
 };
+
+constexpr int kPhaseSlots = 11;   // BatchOut::phase entries per record (8 phases + 3 parts of the narrow sweep)
 
 // Children written by the emit kernel (device-resident frontier format).
 struct ChildOut {

@@ -873,7 +873,21 @@ __device__ __forceinline__ void batch_coef_direct(const NetDev &net, const DD &d
 // (refold_parent).
 template <int CB>
 __device__ __forceinline__ void sweep_narrow(const NetDev &net, DD &d, BatchView &bv, const Pool &pool, int nb,
-                                             double rv, int kS, int kend = INT_MAX) {
+                                             double rv, int kS, int kend = INT_MAX, uint64_t *nclk = nullptr) {
+    // profiling build only: the sweep's clock split into merged layers [0], group switches and
+    // set-up [1], folded runs [2] (nclk: the batch sweeps give it, the other callers do not)
+#ifdef SGUFP_PHASES
+    uint64_t nt = wall_clock64();
+    auto nstamp = [&](int k) {
+        if (nclk) {
+            const uint64_t now = wall_clock64();
+            nclk[k] += now - nt;
+            nt = now;
+        }
+    };
+#else
+    auto nstamp = [](int) {};
+#endif
     constexpr int G = kWave / CB;
     constexpr int PC = kStageEntries / kWave, PT = kTopoEntries / kWave;
     const int c = lane() % CB, grp = lane() / CB;
@@ -970,26 +984,31 @@ __device__ __forceinline__ void sweep_narrow(const NetDev &net, DD &d, BatchView
     // Exact run [ka, kb] of odd depth D (see the call site).  Every node has one in-arc, so
     // a node's value is the fold of its ancestors' steps from layer ka - 1,
     // x = !in ? DMIN : (reg ? x + coef : x) -- the same operations in the same order as
-    // layer by layer.  Lanes are (node of layer kb, cut) pairs: item i = pass * G + grp,
-    // cut c.  A lane walks up its node's ancestors' topology words (one dependent LDS read
-    // per level, batched over the lane's U items), then loads the root value and the
-    // coefficients of every level in one batch and folds.  Only layer kb goes through LDS;
-    // odd depth puts layers ka - 1 and kb in different value buffers, so items write their
-    // results as they go.  Every alive node of the run is an ancestor of an alive node of
-    // layer kb (the deletion cascade removes childless parents), so the width-1 summaries
-    // and walk state2 of the inner layers are written on the way (lanes that share an
-    // ancestor write the same value; items past the layer repeat its last node).
+    // layer by layer.  A lane holds a node of layer kb (item i = base + u * 64 + lane) and
+    // the CB cut values of that node in registers.  It walks up the node's ancestors'
+    // topology words once for all the cuts (one dependent LDS read per level), then loads
+    // the CB parent values (contiguous in LDS: wide reads) and the coefficients of every
+    // level and cut in one batch, folds each cut and writes the CB results with wide
+    // writes.  The cuts are loaded and folded in blocks of CC, so the registers of a block
+    // do not grow with CB.  Cuts >= nb carry whatever the value buffers hold; only their
+    // summaries must not be written.  Only layer kb goes through LDS; odd depth puts layers
+    // ka - 1 and kb in different value buffers, so items write their results as they go.
+    // Every alive node of the run is an ancestor of an alive node of layer kb (the deletion
+    // cascade removes childless parents), so the width-1 summaries and walk state2 of the
+    // inner layers are written on the way (lanes that share an ancestor write the same
+    // value; items past the layer repeat its last node).
     auto fold_run = [&](auto Dc, int ka, int slot_, int k0_, int kw_, uint32_t gn0_) {
         constexpr int D = decltype(Dc)::value;
         const int kb = ka + D - 1;
         const LDS uint16_t *tr = bv.tring + (size_t)slot_ * kTopoEntries;
-        const LDS double *ring_c = bv.cring + (size_t)slot_ * kStageEntries + c * us;
+        const LDS double *ring = bv.cring + (size_t)slot_ * kStageEntries;
         const LDS double *pb = bv.vb + (size_t)((ka - 1) & 1) * kLdsBatchWidth * CB;
         LDS double *ob = bv.vb + (size_t)(kb & 1) * kLdsBatchWidth * CB;
         const int l0 = ka - k0_, lw = ka - kw_;   // ring / metadata-window positions
         uint32_t ebase[D], nofs[D];
         bool w1s[D], wrs[D];
         bool outs = false;   // some layer of the run has a summary or a walk value to store
+        bool inner = false;  // ... other than the walk value of the run's last layer
 #pragma unroll
         for (int s = 0; s < D; s++) {
             nofs[s] = rl(m_noff, lw + s);
@@ -997,17 +1016,16 @@ __device__ __forceinline__ void sweep_narrow(const NetDev &net, DD &d, BatchView
             w1s[s] = (rl(m_pk, lw + s) >> 31) != 0;
             wrs[s] = ((rl(m_pk, lw + s) >> 30) & 1u) != 0;
             outs |= w1s[s] | wrs[s];
+            inner |= w1s[s] | (wrs[s] & (s < D - 1));
         }
         const uint32_t nlast = rl(m_pk, lw + D - 1) & 255u;
-        const bool wlane = c == nb - 1;   // the lane whose cut's state2 the path walks read
-        auto items = [&](auto Uc, uint32_t base) {
+        auto nodes = [&](auto Uc, uint32_t base) {
             constexpr int U = decltype(Uc)::value;
+            constexpr int CC = CB < 4 ? CB : 4, V = CC >= 2 ? 2 : 1;
+            typedef double dv __attribute__((ext_vector_type(V)));
             uint32_t cur[U], wl[U][D];   // wl: topology word | node index << 16, per level
 #pragma unroll
-            for (int u = 0; u < U; u++) {
-                const uint32_t i = base + (uint32_t)(u * G + grp);
-                cur[u] = min(i, nlast - 1u);
-            }
+            for (int u = 0; u < U; u++) cur[u] = min(base + (uint32_t)(u * kWave + lane()), nlast - 1u);
 #pragma unroll
             for (int s = D - 1; s >= 0; s--) {
                 uint32_t w[U];
@@ -1020,50 +1038,93 @@ __device__ __forceinline__ void sweep_narrow(const NetDev &net, DD &d, BatchView
                     cur[u] = mir_parent(w[u]);
                 }
             }
-            double x[U], cf[U][D];
 #pragma unroll
-            for (int u = 0; u < U; u++) {
-                x[u] = pb[cur[u] * CB + c];
+            for (int c0 = 0; c0 < CB; c0 += CC) {
+                dv x[U][CC / V];
+                double cf[U][D][CC];
 #pragma unroll
-                for (int s = 0; s < D; s++)
-                    cf[u][s] = ring_c[(size_t)(l0 + s) * per_layer + mir_rank(wl[u][s])];
-            }
-            sched_fence();
+                for (int u = 0; u < U; u++) {
 #pragma unroll
-            for (int u = 0; u < U; u++) {
-                double xv = x[u], xs[D];
-                // rank 0 is staged as -0.0 (commit): the add stands for reg ? x + coef : x
-#pragma unroll
-                for (int s = 0; s < D; s++) {
-                    const bool in = (wl[u][s] & kMirIn) != 0;
-                    xs[s] = xv = in ? xv + cf[u][s] : DMIN;
-                }
-                ob[(wl[u][D - 1] >> 16) * CB + c] = xv;
-                // the summaries / walk values of the run's layers: one wave-uniform test, then
-                // one divergent branch per item (the per-layer conditions are wave-uniform)
-                if (outs && (wl[u][D - 1] & kMirAlive) != 0 && cv) {
+                    for (int q = 0; q < CC / V; q++) x[u][q] = *(const LDS dv *)(pb + cur[u] * CB + c0 + q * V);
 #pragma unroll
                     for (int s = 0; s < D; s++) {
-                        if (w1s[s]) {
-                            const uint32_t w = wl[u][s];
-                            const bool in = (w & kMirIn) != 0, reg = (w & (31u << kMirRankShift)) != 0;
-                            const double xp = s ? xs[s ? s - 1 : 0] : x[u];
-                            bv.sm[(size_t)(ka + s) * CB + c] = xs[s];
-                            bv.xm[(size_t)(ka + s) * CB + c] = !in ? DMAX : (reg ? xs[s] : xp + 0.0);
+                        const LDS double *rc = ring + (size_t)(l0 + s) * per_layer + mir_rank(wl[u][s]);
+#pragma unroll
+                        for (int cc = 0; cc < CC; cc++) cf[u][s][cc] = rc[(c0 + cc) * us];
+                    }
+                }
+                sched_fence();
+#pragma unroll
+                for (int u = 0; u < U; u++) {
+                    const uint32_t node = wl[u][D - 1] >> 16;
+                    const bool alive = (wl[u][D - 1] & kMirAlive) != 0;
+                    dv xo[CC / V];
+#pragma unroll
+                    for (int cc = 0; cc < CC; cc++) {
+                        double xv = x[u][cc / V][cc % V];
+                        // rank 0 is staged as -0.0 (commit): the add stands for reg ? x + coef : x
+#pragma unroll
+                        for (int s = 0; s < D; s++) {
+                            const bool in = (wl[u][s] & kMirIn) != 0;
+                            xv = in ? xv + cf[u][s][cc] : DMIN;
+                        }
+                        xo[cc / V][cc % V] = xv;
+                    }
+                    // Summaries and walk values: one wave-uniform test, then one divergent branch
+                    // per item.  The usual case is the walk value of the run's last layer alone
+                    // (the parent of a merged layer): the result of cut nb - 1.  A width-1 layer
+                    // or a walk value of an inner layer folds the item's cuts again from the
+                    // registers, the same operations.
+                    if (outs && alive) {
+                        if (inner) {
+#pragma unroll
+                            for (int cc = 0; cc < CC; cc++) {
+                                const int cq = c0 + cc;
+                                if (cq < nb) {
+                                    const double xp0 = x[u][cc / V][cc % V];
+                                    double xv = xp0, xs[D];
+#pragma unroll
+                                    for (int s = 0; s < D; s++) {
+                                        const bool in = (wl[u][s] & kMirIn) != 0;
+                                        xs[s] = xv = in ? xv + cf[u][s][cc] : DMIN;
+                                    }
+#pragma unroll
+                                    for (int s = 0; s < D; s++) {
+                                        if (w1s[s]) {
+                                            const uint32_t w = wl[u][s];
+                                            const bool in = (w & kMirIn) != 0, reg = (w & (31u << kMirRankShift)) != 0;
+                                            const double xp = s ? xs[s ? s - 1 : 0] : xp0;
+                                            bv.sm[(size_t)(ka + s) * CB + cq] = xs[s];
+                                            bv.xm[(size_t)(ka + s) * CB + cq] = !in ? DMAX : (reg ? xs[s] : xp + 0.0);
+                                        }
+                                    }
+                                    if (cq == nb - 1) {
+#pragma unroll
+                                        for (int s = 0; s < D; s++)
+                                            if (wrs[s]) d.s2[nofs[s] + (wl[u][s] >> 16)] = xs[s];
+                                    }
+                                }
+                            }
+                        } else if (nb - 1 >= c0 && nb - 1 < c0 + CC) {
+                            double v = xo[0][0];
+#pragma unroll
+                            for (int cc = 1; cc < CC; cc++) v = (nb - 1 - c0 == cc) ? xo[cc / V][cc % V] : v;
+                            d.s2[nofs[D - 1] + node] = v;
                         }
                     }
-                    if (wlane) {
 #pragma unroll
-                        for (int s = 0; s < D; s++)
-                            if (wrs[s]) d.s2[nofs[s] + (wl[u][s] >> 16)] = xs[s];
-                    }
+                    for (int q = 0; q < CC / V; q++) *(LDS dv *)(ob + node * CB + c0 + q * V) = xo[q];
                 }
             }
         };
-        const uint32_t per = (nlast + G - 1) / G;
-        if (per <= 1) items(std::integral_constant<int, 1>{}, 0u);
-        else
-            for (uint32_t base = 0; base < nlast; base += 2 * G) items(std::integral_constant<int, 2>{}, base);
+        // two nodes per lane only at depth 1, where the wide layers are and the registers allow
+        if constexpr (D == 1) {
+            if (nlast > (uint32_t)kWave) {
+                nodes(std::integral_constant<int, 2>{}, 0u);
+                return;
+            }
+        }
+        for (uint32_t base = 0; base < nlast; base += kWave) nodes(std::integral_constant<int, 1>{}, base);
     };
 
     // the metadata window (base kw) is reloaded only when the next group's prefetch would
@@ -1078,6 +1139,7 @@ __device__ __forceinline__ void sweep_narrow(const NetDev &net, DD &d, BatchView
     uint32_t gn0 = rl(m_noff, 0), gnN = rl(m_noff, k1 - kw) - gn0, ga0 = rl(m_aoff, 0);
     wave_lds_sync();
     const int ke = min(d.kg, kend);   // layers >= kend are not needed (exact redo)
+    nstamp(1);
     for (int k = 1; k < ke;) {
         if (k == k1) {
             // next group: its words and coefficients were issued one group ago
@@ -1096,6 +1158,7 @@ __device__ __forceinline__ void sweep_narrow(const NetDev &net, DD &d, BatchView
             gnN = rl(m_noff, k1 - kw) - gn0;
             ga0 = rl(m_aoff, k0 - kw);
             wave_lds_sync();
+            nstamp(1);
         }
         const int l = k - k0, lm = k - kw;
         const LDS double *coefk = bv.cring + (size_t)slot * kStageEntries + (size_t)l * per_layer;
@@ -1204,6 +1267,7 @@ __device__ __forceinline__ void sweep_narrow(const NetDev &net, DD &d, BatchView
                 }
             }
             wave_lds_sync();
+            nstamp(0);
             k++;
             continue;
         }
@@ -1222,6 +1286,7 @@ __device__ __forceinline__ void sweep_narrow(const NetDev &net, DD &d, BatchView
             default: fold_run(std::integral_constant<int, 5>{}, k, slot, k0, kw, gn0); break;
         }
         wave_lds_sync();
+        nstamp(2);
         k = kb + 1;
     }
 }
@@ -1841,6 +1906,7 @@ struct LoopState {
 #ifdef SGUFP_PHASES
     uint64_t ph[8];   // diagnostic ticks per phase (see BatchOut::phase)
     uint64_t t;       // last stamp
+    uint64_t ns[3];   // the batch sweeps' narrow phase: merged layers, group switches, folded runs
     __device__ __forceinline__ void stamp(int k) {
         uint64_t now = wall_clock64();
         ph[k] += now - t;
@@ -2352,7 +2418,11 @@ __device__ __forceinline__ void cut_loop_batched(const NetDev &net, DD &d, const
         const double rv = root_fold_seq(pool, d, s, total);
         wave_lds_sync();
         st.stamp(4);
+#ifdef SGUFP_PHASES
+        sweep_narrow<CB>(net, d, bv, pool, nb, rv, kS, INT_MAX, st.ns);
+#else
         sweep_narrow<CB>(net, d, bv, pool, nb, rv, kS);
+#endif
         st.stamp(1);
         if (d.kg == 0 && lane() < nb) bv.s2b[lane()] = rv;
         for (int k = max(d.kg, 1); k < last; k++) sweep_tail_layer<CB>(net, d, bv, pool, k, nb, kS);
@@ -2481,7 +2551,7 @@ __global__ void __launch_bounds__(kWave, 2) k_relax(NetDev net, Scratch sc, Batc
     d.aligned = (d.len == d.g) ? 1 : 0;
     int cut_layer = 0;
 #ifdef SGUFP_PHASES
-    LoopState st{kSuccess, in.ub[slot], -1, 0, 0, {0, 0, 0, 0, 0, 0, 0, 0}, t_start};
+    LoopState st{kSuccess, in.ub[slot], -1, 0, 0, {0, 0, 0, 0, 0, 0, 0, 0}, t_start, {0, 0, 0}};
 #else
     LoopState st{kSuccess, in.ub[slot], -1, 0, 0};
 #endif
@@ -2617,7 +2687,8 @@ done:
 #ifdef SGUFP_PHASES
     if (lane() == 0) {
         out.ticks[slot] = wall_clock64() - t_start;
-        for (int k = 0; k < 8; k++) out.phase[(size_t)slot * 8 + k] = st.ph[k];
+        for (int k = 0; k < 8; k++) out.phase[(size_t)slot * kPhaseSlots + k] = st.ph[k];
+        for (int k = 0; k < 3; k++) out.phase[(size_t)slot * kPhaseSlots + 8 + k] = st.ns[k];
     }
 #endif
 }

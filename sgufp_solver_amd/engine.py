@@ -29,7 +29,7 @@ EXPORTS = [
     "sgufp_batch_sync", "sgufp_batch_results", "sgufp_batch_children_size", "sgufp_batch_children",
     "sgufp_batch_paths", "sgufp_batch_stats", "sgufp_batch_refine", "sgufp_set_timing",
     "sgufp_last_timing", "sgufp_probe_network", "sgufp_batch_debug",
-    "sgufp_batch_phases", "sgufp_batch_refold_stats", "sgufp_subproblem", "sgufp_subproblem_detail", "sgufp_slot_keys",
+    "sgufp_batch_phases", "sgufp_batch_narrow_split", "sgufp_batch_refold_stats", "sgufp_subproblem", "sgufp_subproblem_detail", "sgufp_slot_keys",
     "sgufp_cuts_append_rows", "sgufp_frontier_clear", "sgufp_frontier_size", "sgufp_frontier_push",
     "sgufp_frontier_take_size", "sgufp_frontier_take", "sgufp_bnb_step", "sgufp_cuts_rows",
     "sgufp_restricted_relax", "sgufp_restricted_results", "sgufp_restricted_paths", "sgufp_restricted_cutset_size",
@@ -127,6 +127,7 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     lib.sgufp_probe_network.argtypes = [C.c_char_p, P, P, C.c_int32, P, P]
     lib.sgufp_batch_debug.argtypes = [P, P, P]
     lib.sgufp_batch_phases.argtypes = [P, P]
+    lib.sgufp_batch_narrow_split.argtypes = [P, P]
     if hasattr(lib, "sgufp_batch_refold_stats"):   # (an older build named by SGUFP_LIB_PATH for an A/B has none)
         lib.sgufp_batch_refold_stats.argtypes = [P, P]
     lib.sgufp_batch_routes.argtypes = [P, P]
@@ -431,6 +432,13 @@ class Engine:
     def phases(self):
         t = np.zeros((self.n, 8), dtype=np.int64)
         self._check(self.lib.sgufp_batch_phases(self.ctx, _ptr(t)))
+        return t
+
+    def narrow_split(self):
+        """Ticks of the batch sweeps' narrow phase per record, [n, 3]: merged layers, staging-group
+        switches, folded tree runs (profiling library only; zeros otherwise)."""
+        t = np.zeros((self.n, 3), dtype=np.int64)
+        self._check(self.lib.sgufp_batch_narrow_split(self.ctx, _ptr(t)))
         return t
 
     def refold_stats(self):

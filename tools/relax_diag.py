@@ -80,6 +80,8 @@ def main():
     ph = eng.phases() / 100.0
     names = ["build", "narrow", "tail", "last", "post", "redo", "finish", "epilog"]
     print("phase us/node: " + ", ".join(f"{nm} {ph[:, k].mean():.0f}" for k, nm in enumerate(names)))
+    ns = eng.narrow_split() / 100.0
+    print("narrow us/node: " + ", ".join(f"{nm} {ns[:, k].mean():.0f}" for k, nm in enumerate(["merged layers", "group switches", "folded runs"])))
     if args.refold:
         # depth = tree layers folded again between the nearest width-1 summary and the parent
         # layer of a firing merged layer (Engine.refold_stats)
