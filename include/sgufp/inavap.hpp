@@ -196,7 +196,9 @@ class DDSolver {
     int seedWidth = 0;
     int maxIters = 0;
     double roundSecs = 0.0;
+    int selPolicy = SGUFP_SELECT_LIFO;
     double restricted_incumbent(double z);
+    bool gap_reached(double z, int world);
 
   public:
     explicit DDSolver(const std::shared_ptr<Network> &networkPtr_, uint16_t nWorkers, int batch = 4096);
@@ -219,6 +221,15 @@ class DDSolver {
     // the cut added until the path repeats with an unchanged bound -- raises the incumbent to
     // the routing's value, as the reference is seeded with a known value (main.cpp:75)
     void restrictedSeed(int width) { seedWidth = width; }
+    // which open records a round pops once the dive has reached exact leaves:
+    // SGUFP_SELECT_LIFO (the default) the top of the stack, SGUFP_SELECT_BEST_BOUND the ones
+    // with the largest ub (sgufp_frontier_select before every round; shards select locally).
+    // Throws sgufp_error for an unknown policy.
+    void nodeSelection(int policy);
+    // > 0: stop (complete stays false) once gap() <= gapLimit after a round's exchanges, the
+    // bound being max(value, largest ub on any shard's open frontier); checked once an
+    // incumbent exists
+    double gapLimit = 0.0;
     bool complete = false;                           // the last search emptied every frontier
     int64_t maxRounds = 0;                           // stop after this many rounds (0: none)
     double heuristicIncumbent = DOUBLE_MIN;          // the seed's value (DOUBLE_MIN: none)

@@ -321,6 +321,29 @@ int sgufp_incumbent_set(sgufp_ctx *ctx, double value, const int16_t *path, int32
  * the stack, deferred records included, with the bound their loop reached.  One grid-stride
  * kernel over the records' ub (nothing is launched for an empty stack); deterministic. */
 int sgufp_frontier_bound(sgufp_ctx *ctx, double incumbent, double *max_ub, int64_t *open);
+/* Node selection (an extension: the reference's NodeQueue, DDSolver.h, orders by depth only).
+ * Reorders the stack so that the next sgufp_bnb_step(ctx, k, ...) pops the k records with the
+ * largest ub.  k <= 0 means max_batch, a larger k is clamped to max_batch.  With n records on the
+ * stack: order them by ub descending, compared as doubles (-0.0 and 0.0 tie; a NaN ub never
+ * occurs), the record nearer the top first among equal ub; the first k are the selected set.
+ * After the call the other records occupy entries [0, n - k) and the selected ones [n - k, n),
+ * both groups in their previous relative order (a stable partition), every field and solution
+ * entry of a record unchanged; the solution arena is compacted to the records' lengths.  When
+ * the selected records are the top k already -- all ub equal, for instance -- the stack is left
+ * exactly as it was: best-bound degrades to LIFO.  If k >= n, n == 0 or policy is
+ * SGUFP_SELECT_LIFO nothing moves, no kernel is launched and *selected = min(k, n).
+ * *threshold = the smallest ub among the selected records (0.0 for either zero; DOUBLE_MIN when
+ * none).  Either output pointer may be NULL.  The work is on the device, on the context's stream
+ * (a radix select of the k-th largest ub, scans, one scatter into a second set of frontier
+ * arrays that is then swapped in: 21 launches and one small download whatever n).  The second
+ * set doubles the frontier's device memory from the first select that moves records on.
+ * SGUFP_ERR_ARG for an unknown policy; SGUFP_ERR_CAPACITY when the second set or the scratch
+ * cannot be allocated (the stack is untouched).  A select that moved records invalidates a staged
+ * batch as a round does; the stored incumbent, the trace and the deferred records' seen lists
+ * (kept by record content) are unaffected. */
+#define SGUFP_SELECT_LIFO 0         /* no-op */
+#define SGUFP_SELECT_BEST_BOUND 1
+int sgufp_frontier_select(sgufp_ctx *ctx, int k, int policy, int64_t *selected, double *threshold);
 
 /* Read back pool cuts [first, first + count) of one list (insertion order) as dense rows,
  * e.g. to all-gather the cuts a round produced to the other frontier shards. */

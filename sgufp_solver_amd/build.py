@@ -11,6 +11,7 @@
                       GuroSolver / DDSolver, include/sgufp/inavap.hpp) on top of the C ABI
     host_api_test     C++ driver of that API (tests/host/host_api_test.cpp)
     solution_test     C++ driver of the solver's routing / bound / flows (tests/host/solution_test.cpp)
+    select_test       C++ driver of the solver's node selection / gap limit (tests/host/select_test.cpp)
 """
 from __future__ import annotations
 
@@ -29,8 +30,8 @@ ARCH = "gfx950"
 COMMON = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wall", "-Wno-unused-function",
           f"-I{os.path.join(ROOT, 'include')}", f"-I{CSRC}"]
 
-HIP_SOURCES = ["dd_kernels.hip", "sub_kernels.hip", "bnb_kernels.hip", "rdd_kernels.hip", "exact_kernels.hip", "capi.cpp",
-               "bnb.cpp", "network.cpp", "shard.cpp"]
+HIP_SOURCES = ["dd_kernels.hip", "sub_kernels.hip", "bnb_kernels.hip", "rdd_kernels.hip", "exact_kernels.hip",
+               "select_kernels.hip", "capi.cpp", "bnb.cpp", "network.cpp", "shard.cpp"]
 LINK = ["-L/opt/rocm/lib", "-lrccl", "-Wl,-rpath,/opt/rocm/lib"]   # frontier shards (shard.cpp)
 HOST_SOURCES = ["host/inavap.cpp"]
 
@@ -101,8 +102,9 @@ def build_native(force: bool = False, verbose: bool = False) -> str:
             cxx = shutil.which("g++") or "g++"
             _run([cxx, "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall", f"-I{os.path.join(ROOT, 'include')}",
                   *host_srcs, "-o", hlib, f"-L{LIBDIR}", "-lsgufp_hip", "-Wl,-rpath,$ORIGIN"])
-        # C++ drivers of the host API used by tests/test_host_api.py and tests/test_solution_host.py
-        for name in ("host_api_test", "solution_test"):
+        # C++ drivers of the host API used by tests/test_host_api.py, tests/test_solution_host.py
+        # and tests/test_frontier_select.py
+        for name in ("host_api_test", "solution_test", "select_test"):
             tsrc = os.path.join(ROOT, "tests", "host", name + ".cpp")
             texe = os.path.join(LIBDIR, name)
             if os.path.exists(tsrc) and (force or _stale(texe, [tsrc, hlib] + hheaders)):

@@ -75,7 +75,47 @@ void sgufp_ctx::decode_states(const uint16_t *gl, const uint32_t *mask, size_t c
     if (states_off) states_off[count] = ss;
 }
 
+void sgufp_ctx::frontier_alt_drop() {
+    if (fr_alt.gl) release(fr_alt.gl);
+    if (fr_alt.lb) release(fr_alt.lb);
+    if (fr_alt.ub) release(fr_alt.ub);
+    if (fr_alt.mask) release(fr_alt.mask);
+    if (fr_alt.valid) release(fr_alt.valid);
+    if (fr_alt.sol_off) release(fr_alt.sol_off);
+    if (fr_alt.sol_len) release(fr_alt.sol_len);
+    if (fr_alt.sol) release(fr_alt.sol);
+    fr_alt = FrontierDev{};
+    fr_alt_ready = false;
+}
+
+// scratch of one select over n records and the second set of frontier arrays; false (and no
+// second set) when device memory does not allow it
+bool sgufp_ctx::select_reserve(int64_t n) {
+    const size_t nb = (size_t)((n + kSelBlock - 1) / kSelBlock);
+    bool ok = (d_sel_state || alloc(d_sel_state, 1, "frontier select")) &&
+              (d_sel_hist || alloc(d_sel_hist, 256, "frontier select")) &&
+              grow(d_sel_u32, sel_u32_cap, 4 * nb, "frontier select") &&
+              grow(d_sel_i64, sel_i64_cap, 4 * nb, "frontier select");
+    if (ok && !fr_alt_ready) {
+        const size_t cap = (size_t)fr_cap;
+        ok = alloc(fr_alt.gl, cap, "frontier select") && alloc(fr_alt.lb, cap, "frontier select") &&
+             alloc(fr_alt.ub, cap, "frontier select") && alloc(fr_alt.mask, cap, "frontier select") &&
+             alloc(fr_alt.valid, cap, "frontier select") && alloc(fr_alt.sol_off, cap, "frontier select") &&
+             alloc(fr_alt.sol_len, cap, "frontier select") && alloc(fr_alt.sol, fr_sol_cap, "frontier select");
+        if (ok) fr_alt_ready = true;
+        else frontier_alt_drop();
+    }
+    if (!ok) (void)hipGetLastError();   // the failed hipMalloc is reported here, not by a later launch
+    return ok;
+}
+
 bool sgufp_ctx::frontier_reserve(int64_t entries, size_t sol_entries) {
+    // the second set of sgufp_frontier_select keeps the first set's capacities: it goes when
+    // the first set grows, and the next select allocates it again
+    if (fr_alt_ready && (entries > fr_cap || sol_entries > fr_sol_cap)) {
+        if (!sync()) return false;
+        frontier_alt_drop();
+    }
     if (entries > fr_cap) {
         const int64_t cap = std::max<int64_t>(entries, std::max<int64_t>(2 * fr_cap, 4096));
         FrontierDev f{};
@@ -484,6 +524,64 @@ int sgufp_frontier_bound(sgufp_ctx *ctx, double incumbent, double *max_ub, int64
     }
     if (max_ub) *max_ub = mx;
     if (open) *open = cnt;
+    return SGUFP_OK;
+}
+
+// the double whose order-preserving key (ub_key, select_kernels.hip) is `key`; 0.0 for either zero
+static double key_to_ub(uint64_t key) {
+    const uint64_t b = (key >> 63) ? (key & 0x7FFFFFFFFFFFFFFFull) : ~key;
+    double u;
+    std::memcpy(&u, &b, sizeof u);
+    return u;
+}
+
+int sgufp_frontier_select(sgufp_ctx *ctx, int k, int policy, int64_t *selected, double *threshold) {
+    if (!ctx || (policy != SGUFP_SELECT_LIFO && policy != SGUFP_SELECT_BEST_BOUND)) return SGUFP_ERR_ARG;
+    const int64_t n = ctx->fr_n;
+    const int64_t kk = k <= 0 ? ctx->max_batch : std::min(k, ctx->max_batch);
+    if (policy == SGUFP_SELECT_LIFO || n == 0 || kk >= n) {
+        // the top min(k, n) records as they lie: no kernel; their smallest ub comes down only
+        // when the caller asks for it
+        const int64_t m = std::min(kk, n);
+        if (selected) *selected = m;
+        if (threshold) {
+            std::vector<double> ub((size_t)m);
+            if (!ctx->download(ub.data(), ctx->fr.ub + (n - m), (size_t)m) || !ctx->sync()) return SGUFP_ERR_HIP;
+            *threshold = m ? *std::min_element(ub.begin(), ub.end()) : -__DBL_MAX__;
+        }
+        return SGUFP_OK;
+    }
+    if (!ctx->select_reserve(n)) return SGUFP_ERR_CAPACITY;
+    const size_t nb = (size_t)((n + kSelBlock - 1) / kSelBlock);
+    SelBlockCounts bc{};
+    uint32_t *cnt_eq = ctx->d_sel_u32;
+    bc.sel_cnt = ctx->d_sel_u32 + nb;
+    bc.sel_len = ctx->d_sel_u32 + 2 * nb;
+    bc.non_len = ctx->d_sel_u32 + 3 * nb;
+    int64_t *eq_above = ctx->d_sel_i64;
+    bc.sel_cnt_pre = ctx->d_sel_i64 + nb;
+    bc.sel_len_pre = ctx->d_sel_i64 + 2 * nb;
+    bc.non_len_pre = ctx->d_sel_i64 + 3 * nb;
+    SelState s{};
+    s.rank = kk;
+    if (!ctx->upload(ctx->d_sel_state, &s, 1) ||
+        !ctx->hip_ok(hipMemsetAsync(ctx->d_sel_hist, 0, 256 * sizeof(unsigned long long), ctx->stream), "memset") ||
+        !ctx->hip_ok(launch_select(ctx->fr, ctx->fr_alt, n, kk, (int64_t)ctx->fr_sol_cap, ctx->d_sel_state,
+                                   ctx->d_sel_hist, cnt_eq, eq_above, bc, ctx->stream), "frontier select") ||
+        !ctx->download(&s, ctx->d_sel_state, 1) || !ctx->sync())
+        return SGUFP_ERR_HIP;
+    if (s.bad || s.oob || s.sol_top > ctx->fr_sol_top) {   // the stack is as it was: nothing is swapped
+        ctx->err = "frontier select: inconsistent counts";
+        return SGUFP_ERR_STATE;
+    }
+    if (s.moved) {
+        std::swap(ctx->fr, ctx->fr_alt);
+        ctx->fr_sol_top = s.sol_top;   // the spans were compacted to sol_len
+        ctx->relaxed = false;          // a staged batch that aliased the frontier is gone
+        ctx->dd_built = false;
+    }
+    if (selected) *selected = kk;
+    if (threshold) *threshold = key_to_ub(s.prefix);
     return SGUFP_OK;
 }
 

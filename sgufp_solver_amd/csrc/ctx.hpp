@@ -19,6 +19,7 @@
 #include "network.hpp"
 #include "sub_device.hpp"
 #include "rdd_device.hpp"
+#include "select_device.hpp"
 
 namespace sgufp {
 struct Transport;   // shard.cpp
@@ -121,6 +122,19 @@ struct sgufp_ctx {
     size_t fr_sol_cap = 0;
     int64_t fr_sol_top = 0;                   // arena entries in use (host mirror)
     bool frontier_reserve(int64_t entries, size_t sol_entries);
+    // sgufp_frontier_select (select_kernels.hip): the second set of frontier arrays the scatter
+    // writes -- allocated by the first select that moves records, always of the capacities
+    // fr_cap / fr_sol_cap (frontier_reserve drops it when the first set grows) -- and the scratch
+    // of the radix select and the scans
+    FrontierDev fr_alt{};
+    bool fr_alt_ready = false;
+    void frontier_alt_drop();
+    SelState *d_sel_state = nullptr;
+    unsigned long long *d_sel_hist = nullptr;   // [256]
+    uint32_t *d_sel_u32 = nullptr;              // [4 * sel_blocks]
+    int64_t *d_sel_i64 = nullptr;               // [4 * sel_blocks]
+    size_t sel_u32_cap = 0, sel_i64_cap = 0;
+    bool select_reserve(int64_t n);
     // B&B step staging (host mirrors + small device index arrays)
     int32_t *d_bidx = nullptr;                // [max_batch] node indices (paths / parents)
     int32_t *d_perm = nullptr;                // [max_batch] k_relax dispatch order (relax_current)

@@ -294,6 +294,22 @@ void DDSolver::roundLimits(int maxRefineIters, double roundSeconds) {
     dev.check(sgufp_bnb_set_limits(dev.get(), maxRefineIters, roundSeconds), "round limits");
 }
 
+void DDSolver::nodeSelection(int policy) {
+    if (policy != SGUFP_SELECT_LIFO && policy != SGUFP_SELECT_BEST_BOUND)
+        throw sgufp_error("DDSolver::nodeSelection: unknown policy");
+    selPolicy = policy;
+}
+
+// after a round's exchanges: the gap of z to the bound over every shard's open frontier is
+// within gapLimit (z is the same on every shard and the bound is max-reduced: one decision)
+bool DDSolver::gap_reached(double z, int world) {
+    if (!(gapLimit > 0.0) || z == DOUBLE_MIN) return false;
+    double mx = DOUBLE_MIN;
+    dev.check(sgufp_frontier_bound(dev.get(), z, &mx, nullptr), "frontier bound");
+    if (world > 1) dev.check(sgufp_incumbent_allreduce(dev.get(), &mx), "bound all-reduce");
+    return (std::max(z, mx) - z) / std::max(1.0, std::fabs(z)) <= gapLimit;
+}
+
 // The restricted-DD seed on the root record (NodeExplorer.cpp:605-664, the exact-tree loop of
 // processX3; sgufp_solver_amd/restricted.py is the same loop): relax, then until the max path
 // repeats with an unchanged bound, solve its subproblem and add the cut to the pool.  Returns
@@ -385,6 +401,8 @@ double DDSolver::startSolver(double known_optimal) {
             dev.check(sgufp_bnb_set_limits(g, maxIters, secs), "round limits");
         }
         sgufp_bnb_stats st{};
+        if (selPolicy != SGUFP_SELECT_LIFO && !diving)
+            dev.check(sgufp_frontier_select(g, batch, selPolicy, nullptr, nullptr), "node selection");
         dev.check(sgufp_bnb_step(g, diving ? std::min(batch, kDiveBatch) : batch, &z, &st), "B&B round");
         if (st.exact > 0) diving = false;
 #ifdef SOLVER_COUNTERS
@@ -418,7 +436,7 @@ double DDSolver::startSolver(double known_optimal) {
                 complete = true;
                 break;
             }
-            if (over) break;
+            if (over || gap_reached(z, world)) break;
             continue;
         }
         // the round's exchanges between the shards (shard.cpp)
@@ -435,7 +453,7 @@ double DDSolver::startSolver(double known_optimal) {
         // every shard stops in the same round once one of them is over the budget
         double stop = over ? 1.0 : 0.0;
         dev.check(sgufp_incumbent_allreduce(g, &stop), "budget all-reduce");
-        if (stop > 0.0) break;
+        if (stop > 0.0 || gap_reached(z, world)) break;
         dev.check(sgufp_frontier_balance(g, &got), "work sharing");
         received += got;
         if (st.exact > 0 || got > 0) diving = false;

@@ -44,6 +44,10 @@ EXPORTS = [
 ]
 
 
+SELECT_LIFO = 0          # SGUFP_SELECT_LIFO: sgufp_frontier_select does nothing
+SELECT_BEST_BOUND = 1    # SGUFP_SELECT_BEST_BOUND
+
+
 class BnbStats(C.Structure):
     """sgufp_bnb_stats (include/sgufp_hip.h)."""
     _fields_ = [(f, C.c_int64) for f in (
@@ -175,6 +179,7 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     lib.sgufp_incumbent_set.argtypes = [P, C.c_double, P, C.c_int32]
     lib.sgufp_incumbent_sync.argtypes = [P, C.c_double]
     lib.sgufp_frontier_bound.argtypes = [P, C.c_double, P, P]
+    lib.sgufp_frontier_select.argtypes = [P, C.c_int, C.c_int, P, P]
     lib.sgufp_dd_build.argtypes = [P]
     lib.sgufp_dd_apply.argtypes = [P, C.c_int, C.c_int, C.c_double, C.c_int64, P, P, C.c_double, P]
     lib.sgufp_dd_solution.argtypes = [P, C.c_int, P, P]
@@ -722,6 +727,14 @@ class Engine:
         mx, cnt = C.c_double(0.0), C.c_int64(0)
         self._check(self.lib.sgufp_frontier_bound(self.ctx, C.c_double(incumbent), C.byref(mx), C.byref(cnt)))
         return mx.value, cnt.value
+
+    def frontier_select(self, k: int = 0, policy: int = SELECT_BEST_BOUND) -> Tuple[int, float]:
+        """Reorder the stack so that the next bnb_step(z, k) pops the k records with the largest
+        ub (sgufp_frontier_select; frontier.select_order states the rule).  k = 0: max_batch.
+        Returns (selected, threshold): the records selected and the smallest ub among them."""
+        sel, thr = C.c_int64(0), C.c_double(0.0)
+        self._check(self.lib.sgufp_frontier_select(self.ctx, int(k), int(policy), C.byref(sel), C.byref(thr)))
+        return sel.value, thr.value
 
     def bnb_set_trace(self, on: bool = True):
         """Keep what each bnb_step round did (sgufp_bnb_set_trace) for bnb_trace()."""

@@ -42,7 +42,8 @@ class DDSolver:
                  max_batch: int = 4096, batch_nodes: int = 0, engine=None, group=None, verbose: bool = True,
                  progress: float = 0.0, max_rounds: int = 0, dive_batch: int = 64, time_budget: float = 0.0,
                  restricted_width: int = 0, round_seconds: float = 0.0, round_iters: int = 0,
-                 native_world: int = 0, comm=None, stop_rounds: int = 0):
+                 native_world: int = 0, comm=None, stop_rounds: int = 0, node_selection: str = "lifo",
+                 gap_limit: float = 0.0):
         """n_workers is accepted for API compatibility with the reference (threads there);
         the parallelism here is the batch of ``batch_nodes`` (<= max_batch) records per
         round and one rank per GPU."""
@@ -83,6 +84,17 @@ class DDSolver:
         # bound of one round's exact-leaf refinement loops (0: none; see Engine.bnb_set_limits)
         self.round_seconds = round_seconds
         self.round_iters = round_iters
+        # which open records a round pops once the dive has reached exact leaves: "lifo" the top
+        # of the stack (the reference's workers), "best_bound" the ones with the largest ub
+        # (Engine.frontier_select before every round; the dive itself stays depth-first)
+        if node_selection not in ("lifo", "best_bound"):
+            raise ValueError(f"DDSolver: unknown node_selection {node_selection!r}")
+        if node_selection == "best_bound" and not hasattr(engine, "frontier_select"):
+            raise ValueError("DDSolver: node_selection='best_bound' needs an engine with frontier_select")
+        self.node_selection = node_selection
+        # stop (complete = False) once (bound - z) / max(1, |z|) <= gap_limit, the bound being
+        # max(z, largest ub on any shard's frontier); 0: off.  Needs an engine with frontier_bound
+        self.gap_limit = float(gap_limit)
         self.heuristic_incumbent = None
         self.complete = False
         self.counters = {}
@@ -155,6 +167,8 @@ class DDSolver:
         self.complete = False
         t_start = time.perf_counter()
         limits = hasattr(eng, "bnb_set_limits")
+        best_bound = self.node_selection == "best_bound"
+        gap_check = self.gap_limit > 0 and hasattr(eng, "frontier_bound")
         while True:
             batch = self.batch_nodes
             if diving:
@@ -167,6 +181,8 @@ class DDSolver:
                 if self.time_budget > 0:
                     secs = max(1e-3, min(left, secs) if secs > 0 else left)
                 eng.bnb_set_limits(self.round_iters, secs)
+            if best_bound and not diving:
+                eng.frontier_select(batch)
             z_round = z
             z, st = eng.bnb_step(z, batch)
             if has_inc and z > z_round:   # the round improved: its leaf's routing
@@ -194,6 +210,8 @@ class DDSolver:
                     break
                 if eng.incumbent_allreduce(1.0 if over else 0.0) > 0.0:
                     break
+                if gap_check and self._gap_reached(z, eng.incumbent_allreduce):
+                    break
                 self.received += eng.frontier_balance()
                 continue
             if comm is None:
@@ -201,6 +219,8 @@ class DDSolver:
                     self.complete = True
                     break
                 if over:
+                    break
+                if gap_check and self._gap_reached(z, None):
                     break
                 continue
             z = comm.allreduce_max(z)
@@ -212,9 +232,23 @@ class DDSolver:
                 break
             if g[:, 1].any():
                 break
+            if gap_check and self._gap_reached(z, comm.allreduce_max):
+                break
             self.received += comm.rebalance(eng, sizes)
         self._finish(z, comm)
         return z
+
+    def _gap_reached(self, z: float, reduce_max) -> bool:
+        """After a round's exchanges, once an incumbent exists: is the gap of z to the bound over
+        every shard's open frontier within gap_limit?  z is the same on every shard and the bound
+        is max-reduced (reduce_max; None for one shard), so all of them decide alike."""
+        from .solution import gap_of
+        if z == DOUBLE_MIN:
+            return False
+        mx, _ = self.eng.frontier_bound(z)
+        if reduce_max is not None:
+            mx = reduce_max(mx)
+        return gap_of(z, max(z, mx), False) <= self.gap_limit
 
     def _finish(self, z: float, comm):
         """After the last round (complete or stopped): one exchange fixes which shard's routing
