@@ -191,7 +191,17 @@ int sgufp_batch_routes(sgufp_ctx *ctx, int32_t *route);
  * (ray of the first infeasible scenario, grb.cpp:288-350), -1 invalid path / numerical
  * failure.  rhs[k], rows[k * (n_slots + 1) ...] (dense coefficient row, slot keys from
  * sgufp_slot_keys, last entry 0) and obj_mean[k] = sum_s objective_s / S; any output
- * pointer may be NULL.  Paths longer than totalLayers are an argument error. */
+ * pointer may be NULL.  Paths longer than totalLayers are an argument error.
+ * Input domain (all subproblem calls and sgufp_bnb_step; checked on first use, before anything is
+ * allocated or launched -- outside it the call returns SGUFP_ERR_CAPACITY and sgufp_last_error
+ * names the limit): an acyclic network without parallel arcs; n, m <= 32767 and
+ * 2 (m + n + 1) <= 65535; 0 <= lb <= 32767 and -32768 <= ub <= 32767 (ub < 0 <= lb makes the
+ * scenario infeasible); sum |reward| <= 2^31 - 1 and (n + 2) * (2 + 4 sum |reward| (max ub + 1))
+ * < 2^45; at most 160 KiB of LDS per scenario.  Every node without in-arcs is a free supply and
+ * every node without out-arcs a free demand; an arc from the one straight to the other carries and
+ * earns nothing (the reference empties that arc set, Network.cpp:80), and lb > 0 on it makes the
+ * scenario infeasible.  A path whose decisions are not a matching of out-arcs, or that joins more
+ * than 64 arcs into one chain, comes back as type -1 on its own. */
 int sgufp_subproblem(sgufp_ctx *ctx, int n, const int64_t *path_off, const int16_t *paths, int32_t *type,
                      double *rhs, double *rows, double *obj_mean);
 /* Per (path, scenario) detail of the last sgufp_subproblem call, [n * S] each: status (0

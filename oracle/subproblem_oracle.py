@@ -183,7 +183,8 @@ def dual_lp(net: SubNet, y: Dict[Tuple[int, int, int], int], s: int):
 
 def primal_lp(net: SubNet, y: Dict[Tuple[int, int, int], int], s: int):
     """The primal the dual above belongs to: max sum r x, conservation at nodes with in- and
-    out-arcs, l <= x <= u, and the V-bar coupling rows (lambda, mu, sigma, phi)."""
+    out-arcs, l <= x <= u, and the V-bar coupling rows (lambda, mu, sigma, phi); arcs from a node
+    without in-arcs to a node without out-arcs (A4) are left out as the dual leaves them out."""
     n, m = net.n, net.m
     T, H = net.tails, net.heads
     vb = set(int(v) for v in net.vbar)
@@ -222,6 +223,15 @@ def primal_lp(net: SubNet, y: Dict[Tuple[int, int, int], int], s: int):
             Aub.append(r4); bub.append(float(net.ub[bo, s]) * tot)
     c = -np.array([float(net.reward[a, 0]) for a in range(m)])
     bounds = [(float(net.lb[a, s]), float(net.ub[a, s])) for a in range(m)]
+    for a in range(m):
+        if not ins[int(T[a])] and not outs[int(H[a])]:
+            # A4 (source -> sink) is emptied (Network.cpp:80): the dual has no row for the arc, so
+            # it carries and earns nothing; its beta / gamma stay in the dual objective, which
+            # l > 0 or u < 0 make unbounded
+            if net.lb[a, s] > 0 or net.ub[a, s] < 0:
+                return "infeasible", None
+            c[a] = 0.0
+            bounds[a] = (0.0, 0.0)
     res = linprog(c, A_ub=np.array(Aub) if Aub else None, b_ub=np.array(bub) if bub else None,
                   A_eq=np.array(Aeq) if Aeq else None, b_eq=np.array(beq) if beq else None,
                   bounds=bounds, method="highs")

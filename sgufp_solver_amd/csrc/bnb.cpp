@@ -777,9 +777,10 @@ struct BnbRound {
             const int nf = (int)fresh.size();
             int most = 0;
             for (int k : fresh) most = std::max(most, ++nseen[k]);
+            if (!c.sub_init()) return c.sub_rc;
             if (!c.loop_reserve(b, most) || !c.upload(c.d_lact, fresh.data(), (size_t)nf) ||
                 !c.hip_ok(launch_seen_append(o, c.seen, c.d_lact, nf, c.net.m, c.stream), "k_seen_append") ||
-                !c.sub_init() || !c.sub_grow(nf, 1) || !c.grow_rows(c.n_rows + nf))
+                !c.sub_grow(nf, 1) || !c.grow_rows(c.n_rows + nf))
                 return SGUFP_ERR_HIP;
             SubIO io;
             if (!sub_io(nf, nct, io) || !c.hip_ok(launch_subproblem(c.sn, io, c.stream), "subproblem launch"))

@@ -727,18 +727,33 @@ int sgufp_slot_keys(const sgufp_ctx *ctx, uint64_t *keys) {
 }
 
 // ---- scenario subproblem ------------------------------------------------------------
+// every arc sits in one chain, so M = 1 + sum_chains 2 |R| (U + 1) (k_sub_scenario) is at most
+// 1 + 2 sum_a |r_a| (max u + 1); residual costs are below |R| + M <= 2 M
+static int64_t sub_cost_bound(int64_t sum_abs_reward, int64_t umax) { return 2 * (1 + 2 * sum_abs_reward * (umax + 1)); }
+
+bool sgufp_ctx::sub_reject(const char *why) {
+    err = why;
+    sub_rc = SGUFP_ERR_CAPACITY;
+    return false;
+}
+
+// The input domain of the subproblem kernels (include/sgufp_hip.h): whatever lies
+// outside is rejected here, before anything is allocated or launched.
 bool sgufp_ctx::sub_init() {
     if (sub_ready) return true;
+    sub_rc = SGUFP_ERR_HIP;
     const Network &N = net;
     const int n = N.n, m = N.m, S = N.S;
     // chain records keep node / arc ids and bounds in 16 bits (ids already are: Cut.h:342-344)
     // (predecessor words pack arc code << 15 | node: 2 (m + n + 1) codes must fit 16 bits)
-    if (n > 32767 || m > 32767 || 2 * (m + n + 1) > 65535) { err = "subproblem: more than 32766 nodes + arcs"; return false; }
-    for (size_t i = 0; i < N.lb.size(); i++)
-        if (N.lb[i] < -32768 || N.lb[i] > 32767 || N.ub[i] < -32768 || N.ub[i] > 32767) {
-            err = "subproblem: arc bounds outside 16 bits";
-            return false;
-        }
+    if (n > 32767 || m > 32767 || 2 * (m + n + 1) > 65535) return sub_reject("subproblem: more than 32766 nodes + arcs");
+    for (size_t i = 0; i < N.lb.size(); i++) {
+        if (N.lb[i] > 32767 || N.ub[i] < -32768 || N.ub[i] > 32767)
+            return sub_reject("subproblem: arc bounds outside 16 bits (ub in -32768 .. 32767, lb <= 32767)");
+        // the successive shortest paths start at x = 0 and the residual graph has no backward
+        // arc below 0; an unmatched arc is fixed at 0 rather than kept in [l, 0]
+        if (N.lb[i] < 0) return sub_reject("subproblem: negative lower bound (lb must be >= 0)");
+    }
     std::vector<int32_t> zlist;   // free-supply / free-demand nodes (no conservation row)
     for (int v = 0; v < n; v++) {
         const bool src = N.in_arcs[v].empty(), snk = N.out_arcs[v].empty();
@@ -747,8 +762,8 @@ bool sgufp_ctx::sub_init() {
     }
     const int nz = (int)zlist.size();
     // chains are numbered in the topological order of their tails, so that one sweep in
-    // chain order carries a label down a whole run of forward arcs (Kahn's order; on a
-    // cycle the remaining nodes follow in id order -- only the speed depends on it)
+    // chain order carries a label down a whole run of forward arcs (Kahn's order; a network
+    // in which it leaves nodes unranked has a cycle and is rejected)
     std::vector<int32_t> rank(n, -1), indeg(n, 0), arc_topo(m);
     {
         std::vector<int32_t> q;
@@ -760,11 +775,24 @@ bool sgufp_ctx::sub_init() {
             rank[v] = r++;
             for (int a : N.out_arcs[v]) if (--indeg[N.head[a]] == 0) q.push_back(N.head[a]);
         }
-        for (int v = 0; v < n; v++) if (rank[v] < 0) rank[v] = r++;
+        // the successive shortest paths from the zero flow presuppose that no cycle has a positive
+        // reward, and every bound on their length counts on simple source -> sink paths
+        if (r < n) return sub_reject("subproblem: the network has a directed cycle (acyclic networks only)");
         for (int a = 0; a < m; a++) arc_topo[a] = a;
         std::stable_sort(arc_topo.begin(), arc_topo.end(), [&](int a, int b) { return rank[N.tail[a]] < rank[N.tail[b]]; });
     }
-    if (sub_lds_bytes(n, m, m, nz, 4) > 160 * 1024) { err = "network too large for the LDS subproblem"; return false; }
+    if (sub_lds_bytes(n, m, m, nz, 4) > 160 * 1024) return sub_reject("subproblem: network too large for the LDS (160 KiB per scenario)");
+    {
+        // chain reward sums are 32-bit, and the 64-bit Bellman-Ford keys (cost << 16 | hops, inf =
+        // 2^61) carry path costs below 2^45: a path has at most n + 1 residual arcs of cost at most
+        // cost_bound (below) each
+        int64_t sr = 0, umax = 0;
+        for (int a = 0; a < m; a++) sr += std::abs((int64_t)N.reward[(size_t)a * S]);
+        for (size_t i = 0; i < N.ub.size(); i++) umax = std::max<int64_t>(umax, N.ub[i]);
+        if (sr > INT32_MAX) return sub_reject("subproblem: sum of |reward| above 2^31 - 1 (32-bit chain rewards)");
+        if ((int64_t)(n + 2) * sub_cost_bound(sr, umax) >= (int64_t)1 << 45)
+            return sub_reject("subproblem: (n + 2) * cost_bound reaches 2^45 (64-bit keys; cost_bound = 2 + 4 sum|reward| (max ub + 1))");
+    }
     std::vector<int32_t> inner(n), arc_layer(m, -1), lb((size_t)S * m), ub((size_t)S * m), rew(m);
     std::vector<uint8_t> vb(n), in8(n);
     std::vector<int32_t> in_off(n + 1, 0), out_off(n + 1, 0), in_list, out_list;
@@ -816,12 +844,10 @@ bool sgufp_ctx::sub_init() {
         return false;
     sn.n = n; sn.m = m; sn.S = S; sn.L = N.L; sn.n_slots = N.n_slots; sn.nz = nz; sn.zlist = d_z; sn.arc_topo = d_topo; sn.orank = d_orank;
     {
-        // every arc sits in one chain, so M = 1 + sum_chains 2 |R| (U + 1) (k_sub_scenario)
-        // is at most 1 + 2 sum_a |r_a| (max u + 1); residual costs are below R + M <= 2 M
         int64_t sr = 0, umax = 0;
         for (int a = 0; a < m; a++) sr += std::abs((int64_t)rew[a]);
         for (size_t i = 0; i < ub.size(); i++) umax = std::max<int64_t>(umax, ub[i]);
-        sn.cost_bound = 2 * (1 + 2 * sr * (umax + 1));
+        sn.cost_bound = sub_cost_bound(sr, umax);
         // 32-bit keys and 8-byte chain records (k_sub_scenario): no lower bound, no negative
         // upper bound (a chain is then never infeasible up front), small rewards, ids and
         // upper bounds (11-bit fields)
@@ -949,7 +975,7 @@ int sgufp_subproblem(sgufp_ctx *ctx, int n, const int64_t *path_off, const int16
 int sgufp_subproblem_warm(sgufp_ctx *ctx, int n, const int64_t *path_off, const int16_t *paths, const int32_t *warm_src,
                           const int32_t *warm_dst, int32_t *type, double *rhs, double *rows, double *obj_mean) {
     if (!ctx || n < 0 || (n && (!warm_src || !warm_dst))) return SGUFP_ERR_ARG;
-    if (!ctx->sub_init()) return SGUFP_ERR_HIP;
+    if (!ctx->sub_init()) return ctx->sub_rc;
     if (n > ctx->max_batch) return SGUFP_ERR_ARG;
     if (!ctx->warm_reserve()) {
         ctx->err = "warm starts need n + 2 <= 2048 network nodes and device memory for the ring";
@@ -1015,7 +1041,8 @@ static int subproblem_run(sgufp_ctx *ctx, int n, const int64_t *path_off, const 
             return SGUFP_ERR_ARG;
         }
     const size_t total = (size_t)(path_off[n] - path_off[0]);
-    if (!ctx->sub_init() || !ctx->sub_grow(n, std::max<size_t>(total, 1))) return SGUFP_ERR_HIP;
+    if (!ctx->sub_init()) return ctx->sub_rc;
+    if (!ctx->sub_grow(n, std::max<size_t>(total, 1))) return SGUFP_ERR_HIP;
     std::vector<int64_t> off(path_off, path_off + n + 1);
     for (auto &o : off) o -= path_off[0];
     if (!ctx->upload(ctx->d_spoff, off.data(), off.size()) || !ctx->upload(ctx->d_spaths, paths + path_off[0], total))
@@ -1073,7 +1100,7 @@ int sgufp_subproblem_flows(sgufp_ctx *ctx, int n, const int64_t *path_off, const
         ctx->err = "subproblem flows need n + 2 <= 2048 network nodes";
         return SGUFP_ERR_CAPACITY;
     }
-    if (!ctx->sub_init()) return SGUFP_ERR_HIP;
+    if (!ctx->sub_init()) return ctx->sub_rc;
     constexpr size_t kFlowBytes = (size_t)256 << 20;
     const size_t S = (size_t)ctx->net.S, m = (size_t)ctx->net.m, nn = (size_t)ctx->net.n;
     const size_t per = S * (m * sizeof(int16_t) + nn * sizeof(int32_t) + 1);

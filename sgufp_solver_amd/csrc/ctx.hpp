@@ -252,6 +252,10 @@ struct sgufp_ctx {
     bool sub_stats = false;
     double ss[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // launches, scenarios, warm, augs, flow passes, potential passes, fallbacks, cold augs
     void sub_stats_add(int n_paths);
+    // sub_init fails with sub_rc: SGUFP_ERR_CAPACITY when the network or its data lie outside what
+    // the subproblem kernels represent (err names the limit; nothing is launched), else SGUFP_ERR_HIP
+    int sub_rc = 0;
+    bool sub_reject(const char *why);
     bool sub_init();
     bool sub_grow(int n, size_t total);
     bool append_rows(int is_feasibility, int n_cuts, const double *rhs, const std::vector<double> &rows);

@@ -11,7 +11,9 @@
 //      V-bar node: matched pairs carry equal flow (lambda / mu rows), unmatched arcs carry
 //      none (sigma / phi rows).  Following the matching turns every arc into one "chain"
 //      through V-bar nodes; a chain from a non-V-bar tail to a non-V-bar head is one
-//      arc with bounds [max l, min u] and reward sum r, any other chain is fixed at 0.
+//      arc with bounds [max l, min u] and reward sum r, any other chain is fixed at 0
+//      (infeasible if max l > 0 or min u < 0), and so is an arc from a node without in-arcs
+//      straight to a node without out-arcs (the reference's emptied A4 set).
 //   3. Max-reward flow on the contracted DAG (free supply at sources, free demand at
 //      sinks): successive shortest paths (Bellman-Ford in LDS over the residual graph,
 //      Gauss-Seidel sweeps in topological chain order, 64-bit (cost, hops) keys so the
@@ -26,6 +28,13 @@
 //      it.  All of it is integer arithmetic (integral data), written out as f64.
 // A second kernel reduces over scenarios per path in scenario order: the first infeasible
 // scenario's ray (feasibility cut), else the 1/S-weighted sum (optimality cut).
+//
+// Input domain (checked by the host, sgufp_ctx::sub_init, which rejects the rest with
+// SGUFP_ERR_CAPACITY before any launch): an acyclic network -- the successive shortest paths
+// start from the zero flow, which is optimal for no positive-reward cycle only, and every
+// loop bound below (augmentations <= sum of min u, path walks <= n + 2 nodes, Bellman-Ford
+// passes) counts on simple source -> sink paths; lb >= 0 (the residual graph has no backward
+// arc below x = 0); bounds within 16 bits; (n + 2) * cost_bound < 2^45 (64-bit keys).
 //
 // Duals are not unique, so the cut coefficients differ from Gurobi's; what is pinned is
 // the scenario objective (== HiGHS on the reference formulation, tests/), that the cut is
@@ -962,7 +971,7 @@ __device__ __forceinline__ int dec_of(const SubNet &N, const SubIO &io, int64_t 
 
 // ray_mode: r = 0; prescribed targets (ray_p / ray_q) for the chain that certifies an
 // infeasibility up front.  The chain's arcs come from its path's list (k_sub_paths); they are
-// walked twice without per-arc arrays (a lane's chain of up to 63 arcs would otherwise live in
+// walked twice without per-arc arrays (a lane's chain of up to 64 arcs would otherwise live in
 // scratch memory): the first walk gets its length, reward sum, binding arcs and the transfer
 // total of a broken start; the second emits e, the transfers of the matched pairs and sigma /
 // phi, in the order of the closed forms below (all integers: any summation order is exact).
@@ -1015,7 +1024,7 @@ __device__ __forceinline__ ChainOut assemble_chain(const SubNet &N, const WS &W,
         if (len == 0 || x.l > lmax) { lmax = x.l; bmax = len; }
         sumr += x.r;
         if (len > 0) dsum += pres(x.a) - x.r;
-        if (++len >= kMaxChain) { ok = false; return o; }
+        if (++len > kMaxChain) { ok = false; return o; }   // (k_sub_paths flags such a path: cannot happen)
     }
     const bool complete = t >= 0 && h >= 0;
     Arc x = c0, y{};
@@ -1187,7 +1196,7 @@ __global__ void __launch_bounds__(kWave * NW, NW == 1 ? (sizeof(KT) == 4 ? 4 : 3
         }
         W.wa(k, pack_a(t, h, R));
         W.wb(k, pack_b(L, U, x0, first));   // compact: L = 0 (host), no first arc
-        if ((complete && L > U) || (!complete && L > 0)) first_bad = min(first_bad, k);
+        if ((complete && L > U) || (!complete && (L > 0 || U < 0))) first_bad = min(first_bad, k);
     }
     first_bad = B::all(first_bad, [](int x, int y) { return x < y ? x : y; }, W.red);
     B::sync();
@@ -1270,7 +1279,8 @@ __global__ void __launch_bounds__(kWave * NW, NW == 1 ? (sizeof(KT) == 4 ? 4 : 3
         status = kSubError;
         err_site = 8;
     } else if (first_bad != INT_MAX) {
-        // (i) a chain fixed at 0 with a positive lower bound, or (ii) a chain with max l > min u
+        // (i) a chain fixed at 0 with a positive lower bound or a negative upper bound, or (ii) a
+        // chain with max l > min u
         status = kSubInfeasible;
         ray_chain = first_bad;
         const int k = first_bad;
@@ -1286,7 +1296,8 @@ __global__ void __launch_bounds__(kWave * NW, NW == 1 ? (sizeof(KT) == 4 ? 4 : 3
             if (u < bu) { bu = u; bq = a; }
         }
         if (complete) { ray_p = bp; ray_q = bq; }
-        else { ray_p = bp; ray_q = -1; }
+        else if (bl > 0) { ray_p = bp; ray_q = -1; }
+        else { ray_p = bq; ray_q = bq; }   // fixed at 0 with u < 0 <= l on one arc: beta = gamma = 1 there
         B::sync();
         for (int v = tid; v <= n; v += T) W.alpha[v] = 0;
         B::sync();
@@ -1519,7 +1530,7 @@ __global__ void __launch_bounds__(kWave * NW, NW == 1 ? (sizeof(KT) == 4 ? 4 : 3
         dual = B::all(dual, [](int64_t x, int64_t y) { return x + y; }, W.red);
         ok = B::any(ok ? 0u : 1u, W.red) == 0;
         if (ray && ray_chain >= 0 && ray_p >= 0 && ray_p == ray_q) {
-            // single arc with l > u: beta = gamma = 1 on it
+            // single arc with l > u (of a chain fixed at 0: with 0 <= l): beta = gamma = 1 on it
             const int64_t d0 = (int64_t)N.ub[so + ray_p] - N.lb[so + ray_p];
             rhs += d0;
             dual += d0;
@@ -1611,6 +1622,10 @@ __global__ void __launch_bounds__(kWave) k_sub_paths(SubNet N, SubIO io) {
                 e = d;
                 R += N.reward[e];
             }
+            // an arc from a node without in-arcs straight to a node without out-arcs (the
+            // reference's A4, which Network.cpp:80 empties: the dual has no row for it) carries
+            // and earns nothing: a chain fixed at 0, infeasible only by its own bounds
+            if (len == 1 && t >= 0 && h >= 0 && is_src(N, t) && is_snk(N, h)) { t = -1; h = -1; }
         }
         const uint32_t incl = wave_scan_incl((uint32_t)len);
         const int o = run + (int)incl - len;
@@ -1808,8 +1823,11 @@ hipError_t launch_scenarios(const SubNet &N, const SubIO &io, hipStream_t st) {
     // the big-M costs fit 32 bits (host bound)
     const bool large = sub_lds_bytes(N.n, N.m, io.nct_cap, N.nz, kLargeWaves, kb, false) > 64 * 1024 &&
                        io.nct_cap > kRegGroupsSmall * kWave && N.cost_bound < ((int64_t)1 << 30);
+    // SGUFP_SUB_WAVES=1 keeps the single-wave kernels; =8 takes the large variant whatever the
+    // LDS size, wherever its 32-bit costs allow it (tests: the eight-wave code on tiny networks)
     const char *ev = getenv("SGUFP_SUB_WAVES");
-    if (large && !(ev && atoi(ev) == 1)) {
+    const int waves = ev ? atoi(ev) : 0;
+    if ((large && waves != 1) || (waves == 8 && N.cost_bound < ((int64_t)1 << 30))) {
         lds = sub_lds_bytes(N.n, N.m, io.nct_cap, N.nz, kLargeWaves, kb, kw);
         if (io.nct_cap <= kRegGroupsLarge * kLargeWaves * kWave && !N.preds_lds)
             hipLaunchKernelGGL((k_sub_scenario<kRegGroupsLarge, int32_t, kLargeWaves, KT, true, WARM>),

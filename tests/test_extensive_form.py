@@ -9,16 +9,7 @@ import pytest
 from oracle import extensive_form as ef
 from oracle import subproblem_oracle as so
 from sgufp_solver_amd import instance
-
-
-def _node_matchings(ins, outs):
-    """All partial matchings between in-arc tails and out-arc heads of one V-bar node."""
-    res = [()]
-    for k in range(1, min(len(ins), len(outs)) + 1):
-        for a in itertools.combinations(ins, k):
-            for b in itertools.permutations(outs, k):
-                res.append(tuple(zip(a, b)))
-    return res
+from tests.helpers.matchings import node_matchings as _node_matchings
 
 
 @pytest.mark.parametrize("seed,S", [(1, 1), (2, 2), (3, 2)])

@@ -85,6 +85,31 @@ def test_oracle_dual_equals_primal(cfg, seed, S, zl):
     assert n_opt > 0 or not zl
 
 
+@pytest.mark.parametrize("lb_last", [0, 2])
+def test_oracle_dual_equals_primal_with_a_source_to_sink_arc(lb_last):
+    """An arc source -> sink (the generator makes none): the reference empties that arc set
+    (A4, Network.cpp:80; the 7j rows are commented out, grb.cpp:126-133), so the dual has no row
+    for the arc and the primal leaves it out; its beta stays in the dual objective, so a positive
+    lower bound on it (here: in the last scenario) makes that scenario infeasible in both."""
+    from sgufp_solver_amd import engine as E
+    from tests.helpers import sub_families as fam
+    inst = fam.direct_arc(2, lb_last)
+    path = os.path.join(tempfile.mkdtemp(prefix="sgufp_sub_"), "net.txt")
+    inst.write(path)
+    net = so.from_instance(inst, E.probe_network(path)[1])
+    base = so.from_instance(fam.make("T2", 2, 2, "plain"), net.layer_arcs)
+    rng = np.random.default_rng(7)
+    for trial in range(4):
+        y = _full_matching(net, rng, p_match=1.0 if trial % 2 == 0 else 0.8)
+        for s in range(net.S):
+            st, obj, _ = so.dual_lp(net, y, s)
+            pst, pobj = so.primal_lp(net, y, s)
+            assert st == pst == ("infeasible" if lb_last and s == net.S - 1 else "optimal")
+            if st == "optimal":
+                assert abs(obj - pobj) <= TOL * max(1.0, abs(obj))
+                assert abs(obj - so.dual_lp(base, y, s)[1]) <= TOL * max(1.0, abs(obj))   # the arc earns nothing
+
+
 def test_path_roundtrip():
     inst, _, net = _net("C2", 1, 1)
     rng = np.random.default_rng(5)
