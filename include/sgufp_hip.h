@@ -158,6 +158,11 @@ int sgufp_dd_cutset(sgufp_ctx *ctx, int node, double ub, int64_t *n_children);
  * phases are stamped only by the profiling build (sgufp_solver_amd/lib_prof, -DSGUFP_PHASES);
  * the production library returns zeros for them. */
 int sgufp_batch_debug(sgufp_ctx *ctx, int64_t *ticks, int32_t *redo);
+/* k_relax launches of the last relax: 1 for a batch that ran whole (2 with the in-order re-run of
+ * the cut-parallel phase's fallbacks); a batch of at least 1.5 times the device's resident
+ * k_relax waves (or any batch under SGUFP_RELAX_CHUNK=<Q>; default Q 32) runs split, as
+ * (1 + ceil(O cuts / Q)) launches on each of SGUFP_RELAX_STREAMS (default 2) chains. */
+int sgufp_relax_launches(const sgufp_ctx *ctx, int64_t *launches);
 /* ticks per phase [n * 8]: build, narrow sweep, tail layers, last layer, replay/post, redo, finish, tail */
 int sgufp_batch_phases(sgufp_ctx *ctx, int64_t *phase);
 /* the narrow-sweep phase of the batch sweeps split [n * 3]: merged layers, staging-group switches (with

@@ -126,6 +126,8 @@ bool sgufp_ctx::init() {
     if (const char *e = getenv("SGUFP_NX_MIN")) nx_min = std::max(1, atoi(e));
     if (const char *e = getenv("SGUFP_NX_SKIP")) nx_skip = std::max(0, atoi(e));
     if (const char *e = getenv("SGUFP_REDO_SWEEP")) sc.redo_sweep = atoi(e) != 0;   // exact redos by sweep (A/B)
+    if (const char *e = getenv("SGUFP_RELAX_CHUNK")) { split_q = std::max(0, atoi(e)); split_forced = true; }
+    if (const char *e = getenv("SGUFP_RELAX_STREAMS")) split_parts = std::max(1, std::min(kRelaxMaxParts, atoi(e)));
     int64_t acap = std::max<int64_t>(1, (int64_t)std::max(0, L - 4) * (kRelaxedMaxWidth - 1) * maxU);
     if (ncap > (int64_t)kParentMask || acap > (int64_t)0x7FFFFFFF) { err = "DD capacity beyond 22-bit indices"; return false; }
     sc.Ncap = (int)ncap;
@@ -150,6 +152,10 @@ bool sgufp_ctx::init() {
     if (cb > 1 && (!alloc(sc.s2b, B * sc.tail_cap * cb, "scratch") || !alloc(sc.sm, B * sc.Tcap * cb, "scratch") ||
                    !alloc(sc.xm, B * sc.Tcap * cb, "scratch") || !alloc(sc.tmir, B * (size_t)sc.tmir_cap, "scratch")))
         return false;
+    if (cb > 1 && split_q > 0) {
+        if (!alloc(sc.resume, B * kResumeWords, "scratch") || !alloc(sc.rgs, B * (size_t)(sc.Tcap + 1), "scratch")) return false;
+        split_min = cus * relax_occupancy(sc.Tcap, sc.Lcap, cb, sc.us) * 3 / 2;
+    }
     // per-slot refold diagnostics of the exact redos (sgufp_batch_refold_stats; off by default)
     if (const char *e = getenv("SGUFP_REFOLD_STATS"))
         if (atoi(e) != 0 && cb > 1 && !alloc(sc.rstat, B * kRefoldStats, "scratch")) return false;
@@ -438,6 +444,17 @@ bool sgufp_ctx::nx_prepare(int no) {
     return true;
 }
 
+bool sgufp_ctx::split_prepare() {
+    if (split_ready) return true;
+    if (!hip_ok(hipEventCreateWithFlags(&split.fork, hipEventDisableTiming), "event")) return false;
+    for (int k = 0; k + 1 < split_parts; k++)
+        if (!hip_ok(hipStreamCreateWithFlags(&split.extra[k], hipStreamNonBlocking), "stream") ||
+            !hip_ok(hipEventCreateWithFlags(&split.join[k], hipEventDisableTiming), "event"))
+            return false;
+    split_ready = true;
+    return true;
+}
+
 bool sgufp_ctx::relax_current(double optimal_lb) {
     // the slots' meta[5] become pool cut indices: the sgufp_dd_* view of the batch ends here
     dd_built = false;
@@ -447,8 +464,15 @@ bool sgufp_ctx::relax_current(double optimal_lb) {
     if (!relax_order(in)) return false;
     const Pool p = pool();
     hipStream_t st = stream;
+    // a tail worth filling exists only where the batch is well past the device's k_relax waves
+    const bool do_split = sc.resume && split_q > 0 && (split_forced || in.n >= split_min);
+    if (do_split && !split_prepare()) return false;
+    split.q = do_split ? split_q : 0;
+    split.parts = split_parts;
+    relax_launches = 0;
+    split.launches = &relax_launches;
     if (timing) hipEventRecord(ev[0], st);
-    if (!hip_ok(launch_relax(nd, sc, in, p, out, optimal_lb, cb, ex, cus, st), "k_relax")) return false;
+    if (!hip_ok(launch_relax(nd, sc, in, p, out, optimal_lb, cb, ex, cus, st, &split), "k_relax")) return false;
     if (timing) hipEventRecord(ev[1], st);
     return emit_current(in, p);
 }
@@ -1430,6 +1454,13 @@ int sgufp_batch_refine(sgufp_ctx *ctx, int n, const int32_t *node_idx, const uin
                      "k_refine"))
         return SGUFP_ERR_HIP;
     return ctx->sync() ? SGUFP_OK : SGUFP_ERR_HIP;
+}
+
+int sgufp_relax_launches(const sgufp_ctx *ctx, int64_t *launches) {
+    if (!ctx || !launches) return SGUFP_ERR_ARG;
+    if (!ctx->relaxed) return SGUFP_ERR_STATE;
+    *launches = (int64_t)ctx->relax_launches;
+    return SGUFP_OK;
 }
 
 int sgufp_batch_phases(sgufp_ctx *ctx, int64_t *phase) {

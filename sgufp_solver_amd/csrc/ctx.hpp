@@ -31,7 +31,8 @@ hipError_t launch_warm_pick(const SubIO &io, const WarmRing &wr, int ptr, hipStr
 hipError_t launch_flow_summary(int P, int S, int m, const int32_t *reward, int16_t *x, const uint8_t *ok,
                                double *flow_reward, double *mean_flow, hipStream_t st);
 hipError_t launch_relax(const NetDev &, const Scratch &, const BatchIn &, const Pool &, const BatchOut &, double, int,
-                        const ExactIO &, int, hipStream_t);
+                        const ExactIO &, int, hipStream_t, const RelaxSplit *);
+int relax_occupancy(int Tcap, int Lcap, int cb, int us);
 // exact_kernels.hip
 hipError_t launch_exact_cols(const double *rows, const double *rhs, const int32_t *o_order, int no, int first,
                              int stride, int n_slots, int ostride, double *coefO, int reverse, hipStream_t st);
@@ -313,6 +314,21 @@ struct sgufp_ctx {
     bool nx_prepare(int no);
     bool exact_prepare();
 
+    // Split relaxation (launch_relax): a batch of at least split_min records -- one and a half
+    // times the k_relax waves the device holds (CUs x the kernel's occupancy) -- runs as head + chunk
+    // launches of split_q pool positions on split_parts in-order chains, so that the tail of one
+    // chain's launch is filled by the other's next launch; smaller batches keep the single launch
+    // (C4, 16 F + 64 O, 2 048 resident waves: 2 560 records lose 8 % split, 3 072 gain 6 %, DESIGN.md
+    // section 5).  SGUFP_RELAX_CHUNK=<Q> forces the split for every batch (0: never),
+    // SGUFP_RELAX_STREAMS the number of chains.  The extra streams and the events are made by the
+    // first split, without a host synchronisation.
+    int split_q = 32, split_parts = 2, split_min = 0;
+    bool split_forced = false;
+    RelaxSplit split{};
+    bool split_ready = false;
+    bool split_prepare();
+    unsigned long long relax_launches = 0;    // k_relax launches of the last relaxation (sgufp_relax_launches)
+
     bool timing = false;
     hipEvent_t ev[4] = {};
     float ms_relax = 0, ms_emit = 0;
@@ -323,6 +339,11 @@ struct sgufp_ctx {
         for (auto &b : allocs) (void)hipFree(b.p);
         for (auto &e : ev)
             if (e) (void)hipEventDestroy(e);
+        if (split.fork) (void)hipEventDestroy(split.fork);
+        for (auto &e : split.join)
+            if (e) (void)hipEventDestroy(e);
+        for (auto &s : split.extra)
+            if (s) (void)hipStreamDestroy(s);
         if (stream) (void)hipStreamDestroy(stream);
     }
 

@@ -4,6 +4,8 @@
 
 #include <cstdint>
 
+#include <hip/hip_runtime_api.h>
+
 // Device code sees every HBM pointer of the structs below in the global address space, so
 // the compiler emits global_load/global_store (vmcnt only) instead of flat_* accesses, which
 // would make every LDS access wait for all outstanding HBM loads.  The host sees plain
@@ -101,8 +103,39 @@ struct Scratch {
     // 3 most refolds in one redo, 4 refolds in feasibility batches, 5 redos with a refold,
     // 6 + d refolds of depth d (the last entry: that depth or deeper)
     uint32_t SGUFP_GBL *rstat;
+    // resume state of a record whose cut loop a split relaxation suspended between two batches
+    // (status kRelaxPending, see RelaxPart): kResumeWords words -- pool position, flags (1 screened,
+    // 2 hand-off tried), applied, redo, kg, Nn, Amir, ng, DD nodes / arcs / merged arcs -- and the
+    // staging groups of the narrow sweep, [Tcap + 1].  The layer table, the DD scalars, last_cut and
+    // ub go through lay / meta / ubv, the root solution's slots through rslot.  Null unless CB > 1.
+    int32_t SGUFP_GBL *resume;
+    uint16_t SGUFP_GBL *rgs;
 };
 constexpr int kRefoldStats = 16;
+constexpr int kResumeWords = 12;
+
+// Split relaxation (launch_relax): k_relax<CB, kRelaxHead> builds the DD, runs the feasibility
+// batches and the screen and suspends before the first in-order optimality batch;
+// k_relax<CB, kRelaxChunk> resumes the suspended records of its part and runs batches until q more
+// pool positions are consumed (q = 0: to the end).  A suspension falls between two batches only,
+// so every operation of a record and their order are those of the whole kernel.  The status
+// kRelaxPending never leaves launch_relax: the last chunk launch of a part has q = 0.
+constexpr int kRelaxWhole = 0, kRelaxHead = 1, kRelaxChunk = 2;
+constexpr int32_t kRelaxPending = 8;
+struct RelaxPart {
+    int first;   // workgroup b relaxes dispatch position first + b
+    int q;       // chunk launches: pool positions per launch, 0 = no limit
+};
+constexpr int kRelaxMaxParts = 4;
+// host side of a split relaxation (launch_relax): q pool positions per chunk launch, the dispatch
+// order in `parts` chains -- the first on the caller's stream, the others on extra[] -- the events
+// of the fork and the joins, and a counter of k_relax launches (tests)
+struct RelaxSplit {
+    int q, parts;
+    hipStream_t extra[kRelaxMaxParts - 1];
+    hipEvent_t fork, join[kRelaxMaxParts - 1];
+    unsigned long long *launches;
+};
 
 // Staged batch of open nodes (Inavap::Node records, DD.h:456-478), SoA.
 struct BatchIn {

@@ -23,6 +23,7 @@
 // compiled with -ffp-contract=off.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <climits>
 #include <cstdint>
 #include <type_traits>
@@ -2377,10 +2378,19 @@ __device__ __forceinline__ bool screen_opt(const NetDev &net, DD &d, BatchView &
     return false;
 }
 
-template <int CB>
+// Where a split relaxation (RelaxPart) suspends and resumes the batched loop: between two batches,
+// at pool position s.  limit: the first optimality position at or past it suspends the loop.
+struct LoopResume {
+    int s;
+    bool screened, nx_tried;
+    int limit;
+    bool suspended;
+};
+
+template <int CB, int MODE = kRelaxWhole>
 __device__ __forceinline__ void cut_loop_batched(const NetDev &net, DD &d, const Scratch &sc, BatchView &bv, const Pool &pool,
                                  double incumbent, LoopState &st, bool efast, const ExactIO *nx = nullptr, int slot = 0,
-                                 int *nx_k0 = nullptr) {
+                                 int *nx_k0 = nullptr, LoopResume *rs = nullptr) {
     const int total = pool.nf + pool.no;
     const int last = d.T - 1;
     bv.gbase = uni(d.noff[d.kg]);
@@ -2390,6 +2400,12 @@ __device__ __forceinline__ void cut_loop_batched(const NetDev &net, DD &d, const
     }
     int s = 0;
     bool screened = pool.nscreen <= 0;
+    bool nx_tried = false;
+    if constexpr (MODE == kRelaxChunk) {
+        s = rs->s;
+        screened = rs->screened;
+        if (rs->nx_tried) nx = nullptr;
+    }
     while (s < total) {
         const bool feas = s < pool.nf;
         if (!feas && !screened) {
@@ -2399,12 +2415,22 @@ __device__ __forceinline__ void cut_loop_batched(const NetDev &net, DD &d, const
             if (pruned) { st.status = kPrunedOptimality; return; }
         }
         if (!feas && efast) { st.status = kExactPending; return; }
+        if constexpr (MODE != kRelaxWhole) {
+            if (!feas && s >= rs->limit) {
+                rs->s = s;
+                rs->screened = screened;
+                rs->nx_tried = nx_tried || rs->nx_tried;
+                rs->suspended = true;
+                return;
+            }
+        }
         // a non-exact DD under a large pool that survived the first nx_skip optimality cuts in
         // order (most records that a cut prunes go there, cheaply): the cut-parallel phase takes
         // the rest of the pool from here (once)
         if (!feas && nx && s >= pool.nf + nx->nx_skip) {
             if (nx_compile(d, sc, *nx, slot, *nx_k0, s - pool.nf)) { st.status = kNxPending; return; }
             nx = nullptr;
+            nx_tried = true;
         }
         const int nb = min(CB, (feas ? pool.nf : total) - s);
         if (lane() < nb) bv.ids[lane()] = seq_id(pool, s + lane());
@@ -2522,21 +2548,47 @@ __device__ __forceinline__ void cut_loop_batched(const NetDev &net, DD &d, const
     }
 }
 
+// the batch buffers of a slot: LDS by the carve, HBM by the slot
+template <int CB>
+__device__ __forceinline__ void relax_batch_view(BatchView &bv, LDS uint8_t *smem, const LdsCarve &cv, const Scratch &sc,
+                                                 int slot) {
+    bv.vb = (LDS double *)(smem + cv.o_buf);
+    bv.cring = (LDS double *)(smem + cv.o_ring);
+    bv.tring = (LDS uint16_t *)(smem + cv.o_tring);
+    bv.coef = (LDS double *)(smem + cv.o_bcoef);
+    bv.w1 = smem + cv.o_w1;
+    bv.ids = (LDS int32_t *)(smem + cv.o_ids);
+    bv.wm = (LDS uint64_t *)(smem + cv.o_wm);
+    bv.fm = bv.wm + (sc.Tcap + 63) / 64;
+    bv.wsel = nullptr;
+    bv.s2b = sc.s2b + (size_t)slot * sc.tail_cap * CB;
+    bv.sm = sc.sm + (size_t)slot * sc.Tcap * CB;
+    bv.xm = sc.xm + (size_t)slot * sc.Tcap * CB;
+    bv.rstat = sc.rstat ? sc.rstat + (size_t)slot * kRefoldStats : nullptr;
+}
+
 // ------------------------------------------------------------------------------------
 // Kernel 1: build + pool sweeps + finish, one wave per open node.
-template <int CB>
+// MODE (dd_device.hpp, RelaxPart): the whole record, or one launch of a split relaxation.
+template <int CB, int MODE = kRelaxWhole>
 __global__ void __launch_bounds__(kWave, 2) k_relax(NetDev net, Scratch sc, BatchIn in, Pool pool, BatchOut out,
-                                                double incumbent, ExactIO ex) {
+                                                double incumbent, ExactIO ex, RelaxPart part) {
+    static_assert(MODE == kRelaxWhole || CB > 1, "only the batched loop suspends");
     extern __shared__ __attribute__((aligned(16))) uint8_t smem_raw[];
     LDS uint8_t *smem = (LDS uint8_t *)smem_raw;
-    if ((int)blockIdx.x >= in.n) return;
-    const int slot = in.perm ? in.perm[blockIdx.x] : (int)blockIdx.x;
+    constexpr bool chunk = MODE == kRelaxChunk;
+    const int wg = part.first + (int)blockIdx.x;
+    if (wg >= in.n) return;
+    const int slot = in.perm ? in.perm[wg] : wg;
     // the re-run after the cut-parallel phase of non-exact DDs: only the records it could
     // not settle (kNxFallback), in order, from scratch
-    if (ex.redo && out.status[slot] != kNxFallback) return;
-    if (sc.rstat && lane() < kRefoldStats) sc.rstat[(size_t)slot * kRefoldStats + lane()] = 0;
+    if (MODE == kRelaxWhole && ex.redo && out.status[slot] != kNxFallback) return;
+    // a chunk launch: only the records an earlier launch of the part suspended
+    if (chunk && out.status[slot] != kRelaxPending) return;
+    if (!chunk && sc.rstat && lane() < kRefoldStats) sc.rstat[(size_t)slot * kRefoldStats + lane()] = 0;
 #ifdef SGUFP_PHASES
     const uint64_t t_start = wall_clock64();
+    uint64_t t_before = 0;   // ticks of the record's earlier launches
 #endif
     DD d;
     dd_bind(d, smem, sc, slot, CB);
@@ -2560,7 +2612,43 @@ __global__ void __launch_bounds__(kWave, 2) k_relax(NetDev net, Scratch sc, Batc
     bool efast = false;
     int nx_k0 = -1;
     d.T = 1; d.exact = 1;
+    LoopResume rs{0, false, false, pool.nf, false};
 
+    if constexpr (chunk) {
+        // restore what the suspending launch saved (see the suspension below), then go on
+        const GBL int32_t *rw = sc.resume + (size_t)slot * kResumeWords;
+        load_meta_layers(d, sc, slot);
+        rs.s = uni(rw[0]);
+        rs.screened = (uni(rw[1]) & 1) != 0;
+        rs.nx_tried = (uni(rw[1]) & 2) != 0;
+        rs.limit = part.q > 0 ? rs.s + part.q : INT_MAX;
+        st.applied = (uint32_t)uni(rw[2]);
+        st.redo = (uint32_t)uni(rw[3]);
+        st.last_cut = uni(sc.meta[(size_t)slot * 8 + 5]);
+        st.ub = sc.ubv[slot];
+        n_nodes = (uint32_t)uni(rw[8]); n_arcs = (uint32_t)uni(rw[9]); n_merged = (uint32_t)uni(rw[10]);
+        LdsCarve cv = lds_carve(sc.Tcap, sc.Lcap, CB, sc.us);
+        d.tmir = sc.tmir + (size_t)slot * sc.tmir_cap;
+        d.gstart = (LDS uint16_t *)(smem + cv.o_gs);
+        d.kg = uni(rw[4]); d.Nn = (uint32_t)uni(rw[5]); d.Amir = (uint32_t)uni(rw[6]); d.ng = uni(rw[7]);
+        d.stream = 1;
+        const GBL int32_t *rsl = sc.rslot + (size_t)slot * sc.Lcap;
+        for (int t = lane(); t < d.len; t += kWave) d.rslot[t] = (int16_t)rsl[t];
+        const GBL uint16_t *gs = sc.rgs + (size_t)slot * (sc.Tcap + 1);
+        for (int k = lane(); k <= d.ng; k += kWave) d.gstart[k] = gs[k];
+        wave_mem_sync();
+#ifdef SGUFP_PHASES
+        t_before = out.ticks[slot];
+        for (int k = 0; k < 8; k++) st.ph[k] = out.phase[(size_t)slot * kPhaseSlots + k];
+        for (int k = 0; k < 3; k++) st.ns[k] = out.phase[(size_t)slot * kPhaseSlots + 8 + k];
+#endif
+        st.stamp(7);   // re-entry: the restore counts as epilogue, like the save
+        BatchView bv;
+        relax_batch_view<CB>(bv, smem, cv, sc, slot);
+        const bool nxtry = ex.enabled && ex.nx && !ex.redo && !d.exact && pool.no >= ex.nx_min;
+        cut_loop_batched<CB, MODE>(net, d, sc, bv, pool, incumbent, st, false, nxtry ? &ex : nullptr, slot, &nx_k0, &rs);
+        goto looped;
+    }
     if (!in.valid[slot] || d.len > d.g || d.g > net.L || d.len > sc.Lcap) {
         st.status = kErrRecord;
         goto done;
@@ -2595,27 +2683,45 @@ __global__ void __launch_bounds__(kWave, 2) k_relax(NetDev net, Scratch sc, Batc
         d.tmir = sc.tmir + (size_t)slot * sc.tmir_cap;
         d.gstart = (LDS uint16_t *)(smem + cv.o_gs);
         BatchView bv;
-        bv.vb = (LDS double *)(smem + cv.o_buf);
-        bv.cring = (LDS double *)(smem + cv.o_ring);
-        bv.tring = (LDS uint16_t *)(smem + cv.o_tring);
-        bv.coef = (LDS double *)(smem + cv.o_bcoef);
-        bv.w1 = smem + cv.o_w1;
-        bv.ids = (LDS int32_t *)(smem + cv.o_ids);
-        bv.wm = (LDS uint64_t *)(smem + cv.o_wm);
-        bv.fm = bv.wm + (sc.Tcap + 63) / 64;
-        bv.wsel = nullptr;
-        bv.s2b = sc.s2b + (size_t)slot * sc.tail_cap * CB;
-        bv.sm = sc.sm + (size_t)slot * sc.Tcap * CB;
-        bv.xm = sc.xm + (size_t)slot * sc.Tcap * CB;
+        relax_batch_view<CB>(bv, smem, cv, sc, slot);
         build_stream(d, n_merged, CB * pool.ustride);   // tmir_cap = Ncap + Acap >= Nn + Amir
-        bv.rstat = sc.rstat ? sc.rstat + (size_t)slot * kRefoldStats : nullptr;
         const bool nxtry = ex.enabled && ex.nx && !ex.redo && !d.exact && pool.no >= ex.nx_min;
-        if (d.stream) cut_loop_batched<CB>(net, d, sc, bv, pool, incumbent, st, efast, nxtry ? &ex : nullptr, slot, &nx_k0);
+        if (d.stream)
+            cut_loop_batched<CB, MODE>(net, d, sc, bv, pool, incumbent, st, efast, nxtry ? &ex : nullptr, slot, &nx_k0, &rs);
         else cut_loop_single(net, d, pool, incumbent, 0, st, efast);
     } else {
         cut_loop_single(net, d, pool, incumbent, 0, st, efast);
     }
+looped: __attribute__((unused));
     st.stamp(6);
+    if (MODE != kRelaxWhole && rs.suspended) {
+        // between two batches: the DD is in the slot's HBM scratch; save the layer table, the
+        // scalars and the loop's position for the part's next launch
+        if (lane() == 0) {
+            GBL int32_t *rw = sc.resume + (size_t)slot * kResumeWords;
+            rw[0] = rs.s; rw[1] = (rs.screened ? 1 : 0) | (rs.nx_tried ? 2 : 0);
+            rw[2] = (int32_t)st.applied; rw[3] = (int32_t)st.redo;
+            rw[4] = d.kg; rw[5] = (int32_t)d.Nn; rw[6] = (int32_t)d.Amir; rw[7] = d.ng;
+            rw[8] = (int32_t)n_nodes; rw[9] = (int32_t)n_arcs; rw[10] = (int32_t)n_merged;
+            out.status[slot] = kRelaxPending;
+        }
+        if (!chunk) {
+            GBL int32_t *rsl = sc.rslot + (size_t)slot * sc.Lcap;
+            for (int t = lane(); t < d.len; t += kWave) rsl[t] = (int32_t)d.rslot[t];
+            GBL uint16_t *gs = sc.rgs + (size_t)slot * (sc.Tcap + 1);
+            for (int k = lane(); k <= d.ng; k += kWave) gs[k] = d.gstart[k];
+        }
+        store_meta_layers(d, sc, slot, st.last_cut, kRelaxPending, 0, st.ub);
+        st.stamp(7);
+#ifdef SGUFP_PHASES
+        if (lane() == 0) {
+            out.ticks[slot] = t_before + (wall_clock64() - t_start);
+            for (int k = 0; k < 8; k++) out.phase[(size_t)slot * kPhaseSlots + k] = st.ph[k];
+            for (int k = 0; k < 3; k++) out.phase[(size_t)slot * kPhaseSlots + 8 + k] = st.ns[k];
+        }
+#endif
+        return;
+    }
     if (st.status == kExactPending || st.status == kNxPending) {
         // hand-off: the root solution's slots for k_exact_root, then one pending entry and
         // this record's leaf passes (a single 64-bit atomic keeps the pass bases ascending
@@ -2686,7 +2792,7 @@ done:
     st.stamp(7);
 #ifdef SGUFP_PHASES
     if (lane() == 0) {
-        out.ticks[slot] = wall_clock64() - t_start;
+        out.ticks[slot] = t_before + (wall_clock64() - t_start);
         for (int k = 0; k < 8; k++) out.phase[(size_t)slot * kPhaseSlots + k] = st.ph[k];
         for (int k = 0; k < 3; k++) out.phase[(size_t)slot * kPhaseSlots + 8 + k] = st.ns[k];
     }
@@ -3220,17 +3326,71 @@ size_t relax_lds_bytes(int Tcap, int Lcap, int cb, int us) { return lds_carve(Tc
 hipError_t launch_exact(const NetDev &net, const Scratch &sc, const ExactIO &ex, double incumbent, int cus,
                         hipStream_t st);
 
+// Resident k_relax waves per compute unit at the cut-batch size cb (its registers and LDS)
+int relax_occupancy(int Tcap, int Lcap, int cb, int us) {
+    const size_t lds = relax_lds_bytes(Tcap, Lcap, cb, us);
+    const auto k = cb == 4 ? k_relax<4> : cb == 8 ? k_relax<8> : cb == 16 ? k_relax<16> : k_relax<1>;
+    int nb = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, k, kWave, lds) != hipSuccess) {
+        (void)hipGetLastError();
+        return 8;
+    }
+    return nb > 0 ? nb : 8;
+}
+
+// The split relaxation (RelaxSplit, ctx.hpp): the dispatch order in sp.parts contiguous parts,
+// each an in-order chain of launches on a stream of its own -- head, then ceil(no / q) chunk
+// launches, the last one without a limit -- so that the draining tail of one chain's launch is
+// filled by the other chain's next one.  Part 0 runs on st; the others fork from it and join it
+// again through events, with no host synchronisation.
+template <int CB>
+static hipError_t relax_split(const NetDev &net, const Scratch &sc, const BatchIn &in, const Pool &pool, const BatchOut &out,
+                              double incumbent, const ExactIO &ex, const RelaxSplit &sp, size_t lds, hipStream_t st) {
+    const int parts = std::max(1, std::min(sp.parts, std::min(in.n, kRelaxMaxParts)));
+    const int nchunk = pool.no > 0 ? (pool.no + sp.q - 1) / sp.q : 0;
+    hipError_t e;
+    if (parts > 1 && (e = hipEventRecord(sp.fork, st)) != hipSuccess) return e;
+    for (int p = 0; p < parts; p++) {
+        const hipStream_t s = p == 0 ? st : sp.extra[p - 1];
+        const int lo = (int)((int64_t)in.n * p / parts), hi = (int)((int64_t)in.n * (p + 1) / parts);
+        if (p > 0 && (e = hipStreamWaitEvent(s, sp.fork, 0)) != hipSuccess) return e;
+        BatchIn part = in;
+        part.n = hi;
+        hipLaunchKernelGGL((k_relax<CB, kRelaxHead>), dim3(hi - lo), dim3(kWave), lds, s, net, sc, part, pool, out, incumbent,
+                           ex, RelaxPart{lo, 0});
+        if (sp.launches) ++*sp.launches;
+        for (int c = 0; c < nchunk; c++) {
+            hipLaunchKernelGGL((k_relax<CB, kRelaxChunk>), dim3(hi - lo), dim3(kWave), lds, s, net, sc, part, pool, out,
+                               incumbent, ex, RelaxPart{lo, c + 1 < nchunk ? sp.q : 0});
+            if (sp.launches) ++*sp.launches;
+        }
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+        if (p > 0 && ((e = hipEventRecord(sp.join[p - 1], s)) != hipSuccess ||
+                      (e = hipStreamWaitEvent(st, sp.join[p - 1], 0)) != hipSuccess))
+            return e;
+    }
+    return hipSuccess;
+}
+
 hipError_t launch_relax(const NetDev &net, const Scratch &sc, const BatchIn &in, const Pool &pool,
-                        const BatchOut &out, double incumbent, int cb, const ExactIO &ex, int cus, hipStream_t st) {
+                        const BatchOut &out, double incumbent, int cb, const ExactIO &ex, int cus, hipStream_t st,
+                        const RelaxSplit *sp) {
     if (in.n <= 0) return hipSuccess;
     size_t lds = relax_lds_bytes(sc.Tcap, sc.Lcap, cb, sc.us);
     // k_relax at the cut-batch size cb (1, 4, 8 or 16; anything else runs single-cut)
     auto relax = [&](const ExactIO &io) {
         const auto k = cb == 4 ? k_relax<4> : cb == 8 ? k_relax<8> : cb == 16 ? k_relax<16> : k_relax<1>;
-        hipLaunchKernelGGL(k, dim3(in.n), dim3(kWave), lds, st, net, sc, in, pool, out, incumbent, io);
+        hipLaunchKernelGGL(k, dim3(in.n), dim3(kWave), lds, st, net, sc, in, pool, out, incumbent, io, RelaxPart{0, 0});
+        if (sp && sp->launches) ++*sp->launches;
         return hipGetLastError();
     };
-    hipError_t e = relax(ex);
+    hipError_t e;
+    if (sp && sp->q > 0 && sc.resume && (cb == 4 || cb == 8 || cb == 16))
+        e = cb == 4 ? relax_split<4>(net, sc, in, pool, out, incumbent, ex, *sp, lds, st)
+          : cb == 8 ? relax_split<8>(net, sc, in, pool, out, incumbent, ex, *sp, lds, st)
+                    : relax_split<16>(net, sc, in, pool, out, incumbent, ex, *sp, lds, st);
+    else
+        e = relax(ex);
     if (e != hipSuccess || !ex.enabled || ex.no <= 0) return e;
     // exact DDs handed off by k_relax: root folds, terminal weights, outcome
     if ((e = launch_exact(net, sc, ex, incumbent, cus, st)) != hipSuccess) return e;
@@ -3276,7 +3436,7 @@ hipError_t launch_dd_build(const NetDev &net, const Scratch &sc, const BatchIn &
     none.ustride = 1;
     ExactIO ex{};
     hipLaunchKernelGGL(k_relax<1>, dim3(in.n), dim3(kWave), relax_lds_bytes(sc.Tcap, sc.Lcap, 1, sc.us), st, net, sc,
-                       in, none, out, DMIN, ex);
+                       in, none, out, DMIN, ex, RelaxPart{0, 0});
     return hipGetLastError();
 }
 

@@ -135,6 +135,8 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     if hasattr(lib, "sgufp_batch_refold_stats"):   # (an older build named by SGUFP_LIB_PATH for an A/B has none)
         lib.sgufp_batch_refold_stats.argtypes = [P, P]
     lib.sgufp_batch_routes.argtypes = [P, P]
+    if hasattr(lib, "sgufp_relax_launches"):   # (an older build named by SGUFP_LIB_PATH has none)
+        lib.sgufp_relax_launches.argtypes = [P, P]
     lib.sgufp_subproblem.argtypes = [P, C.c_int, P, P, P, P, P, P]
     lib.sgufp_subproblem_detail.argtypes = [P, P, P, P]
     lib.sgufp_slot_keys.argtypes = [P, P]
@@ -445,6 +447,13 @@ class Engine:
         t = np.zeros((self.n, 3), dtype=np.int64)
         self._check(self.lib.sgufp_batch_narrow_split(self.ctx, _ptr(t)))
         return t
+
+    def relax_launches(self) -> int:
+        """k_relax launches of the last relaxation (sgufp_relax_launches): 1 for a batch that ran
+        whole, several for one that ran split (SGUFP_RELAX_CHUNK / SGUFP_RELAX_STREAMS)."""
+        v = C.c_int64(0)
+        self._check(self.lib.sgufp_relax_launches(self.ctx, C.byref(v)))
+        return int(v.value)
 
     def refold_stats(self):
         """Per record the refold counters of the last relaxation's exact redos

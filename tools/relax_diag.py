@@ -1,9 +1,18 @@
 """Per-node diagnostics of one relaxation step on the bench workload (GPU).
 
     python tools/relax_diag.py [--config C4 --seed 1 --nodes 4096 --cb 16 --refold]
+                               [--chunk Q --streams S] [--dump FILE.npz]
+    python tools/relax_diag.py --trace KERNEL_TRACE.csv
 
 Prints the k_relax time, the distribution of per-wave wall-clock ticks against DD
-size / status / cuts applied / batched-sweep restarts."""
+size / status / cuts applied / batched-sweep restarts.  --chunk / --streams set the split
+relaxation (SGUFP_RELAX_CHUNK / SGUFP_RELAX_STREAMS; --chunk 0: one launch); --dump writes the
+per-record clocks for tools/tail_sim.py.  The per-wave clocks of a split step are summed over the
+record's launches; phase 7 (epilogue) then holds every save and restore.
+
+--trace reads a `rocprofv3 --kernel-trace --output-format csv` file of a run instead (no GPU):
+per step -- the k_relax launches between two k_scan2 -- every launch's queue, start, duration and
+the time it shared the device with a k_relax launch of another queue."""
 import argparse
 import os
 import sys
@@ -16,6 +25,38 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
+def trace_report(path, steps=2):
+    """Per-launch times of the last `steps` relaxation steps in a rocprofv3 kernel trace."""
+    import csv
+    import re
+    rows = []
+    with open(path) as fh:
+        for r in csv.DictReader(fh):
+            name = r.get("Kernel_Name", "")
+            if "k_relax" in name or "k_scan2" in name:
+                m = re.search(r"k_relax<\d+, (\d)>", name)
+                kind = "scan" if "k_scan2" in name else ("whole", "head", "chunk")[int(m.group(1))] if m else "whole"
+                rows.append((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), r.get("Queue_Id", "?"), kind,
+                             int(r.get("Grid_Size_X", r.get("Grid_Size", 0)) or 0)))
+    rows.sort()
+    groups, cur = [], []
+    for r in rows:
+        if r[3] == "scan":
+            if cur:
+                groups.append(cur)
+            cur = []
+        else:
+            cur.append(r)
+    for g in groups[-steps:]:
+        t0, t1 = g[0][0], max(r[1] for r in g)
+        print(f"step: {len(g)} k_relax launches on {len({r[2] for r in g})} queue(s), {(t1 - t0) / 1e6:.3f} ms "
+              f"from the first start to the last end, {sum(r[1] - r[0] for r in g) / 1e6:.3f} ms summed")
+        for a, b, q, kind, grid in g:
+            shared = sum(max(0, min(b, d) - max(a, c)) for c, d, q2, _, _ in g if q2 != q)
+            print(f"  queue {q} {kind:5s} grid {grid:7d} start {(a - t0) / 1e6:8.3f} ms  {(b - a) / 1e6:7.3f} ms  "
+                  f"shared with another queue {shared / 1e6:7.3f} ms")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", default="C4")
@@ -24,7 +65,17 @@ def main():
     ap.add_argument("--cb", default=None)
     ap.add_argument("--incumbent", default="p40")
     ap.add_argument("--refold", action="store_true", help="also print the exact redos' refold counters")
+    ap.add_argument("--chunk", default=None, help="SGUFP_RELAX_CHUNK (0: one launch)")
+    ap.add_argument("--streams", default=None, help="SGUFP_RELAX_STREAMS")
+    ap.add_argument("--dump", default=None, help="write the per-record clocks (tools/tail_sim.py) to this .npz")
+    ap.add_argument("--trace", default=None, help="a rocprofv3 kernel trace CSV to report on (no GPU)")
     args = ap.parse_args()
+    if args.trace:
+        return trace_report(args.trace)
+    if args.chunk is not None:
+        os.environ["SGUFP_RELAX_CHUNK"] = args.chunk
+    if args.streams is not None:
+        os.environ["SGUFP_RELAX_STREAMS"] = args.streams
     if args.refold:
         os.environ["SGUFP_REFOLD_STATS"] = "1"
     if args.cb:
@@ -65,6 +116,12 @@ def main():
     print(f"cb={os.environ.get('SGUFP_CUT_BATCH', 'default')} inc={inc:.3f} k_relax={ms_relax:.2f} ms "
           f"emit={ms_emit:.3f} ms wall={wall * 1e3:.2f} ms")
     print(f"status {dict(zip(*np.unique(st, return_counts=True)))} exact={int(ex.sum())}")
+    if hasattr(eng.lib, "sgufp_relax_launches"):
+        print(f"k_relax launches {eng.relax_launches()} (SGUFP_RELAX_CHUNK={os.environ.get('SGUFP_RELAX_CHUNK', 'default')}, "
+              f"SGUFP_RELAX_STREAMS={os.environ.get('SGUFP_RELAX_STREAMS', 'default')})")
+    if args.dump:
+        np.savez(args.dump, ticks=ticks, phases=eng.phases(), sweeps=sw, status=st, n_feas=16, n_opt=64,
+                 ms_relax=ms_relax, nodes=args.nodes)
     print(f"wave us: mean {us.mean():.1f} p50 {np.median(us):.1f} p90 {np.percentile(us, 90):.1f} "
           f"max {us.max():.1f}; sum/CU(256) {us.sum() / 256 / 1e3:.2f} ms")
     print(f"dd nodes mean {dn.mean():.0f} max {dn.max()}; sweeps mean {sw.mean():.1f}; redo mean {redo.mean():.2f} "
