@@ -163,6 +163,14 @@ int sgufp_batch_debug(sgufp_ctx *ctx, int64_t *ticks, int32_t *redo);
  * k_relax waves (or any batch under SGUFP_RELAX_CHUNK=<Q>; default Q 32) runs split, as
  * (1 + ceil(O cuts / Q)) launches on each of SGUFP_RELAX_STREAMS (default 2) chains. */
 int sgufp_relax_launches(const sgufp_ctx *ctx, int64_t *launches);
+/* DD templates of the last relax: the relaxed DD of a record depends on its global layer and root
+ * state mask only, so a batch that runs split by the rule above (not by SGUFP_RELAX_CHUNK alone)
+ * builds each (layer, mask) that two or more of its valid, unpruned records with a full-length
+ * solution share once and copies it into those records' slots.  `built`: templates built (at most
+ * the pool's slots, SGUFP_RELAX_TEMPLATE_SLOTS), `instantiated`: records that took a copy; 0, 0 for
+ * a relax without templates.  SGUFP_RELAX_TEMPLATES=1 uses templates for every batch with a cut
+ * batch above 1, 0 for none.  Synchronises the stream. */
+int sgufp_relax_templates(sgufp_ctx *ctx, int64_t *built, int64_t *instantiated);
 /* ticks per phase [n * 8]: build, narrow sweep, tail layers, last layer, replay/post, redo, finish, tail */
 int sgufp_batch_phases(sgufp_ctx *ctx, int64_t *phase);
 /* the narrow-sweep phase of the batch sweeps split [n * 3]: merged layers, staging-group switches (with

@@ -139,7 +139,7 @@ bool sgufp_ctx::init() {
     sc.tmir_cap = cb > 1 ? (int)(sc.Ncap + sc.Acap) : 0;
     sc.tail_cap = (int)tail;
     sc.cb_max = cb;
-    const size_t B = (size_t)max_batch;
+    const size_t B = (size_t)max_batch, held0 = held;
     if (!alloc(sc.ntopo, B * sc.Ncap, "scratch") || !alloc(sc.nflag, B * sc.Ncap, "scratch") ||
         !alloc(sc.nmask, B * sc.Ncap, "scratch") || !alloc(sc.outcnt, B * sc.Ncap, "scratch") ||
         !alloc(sc.s2, B * sc.Ncap, "scratch") || !alloc(sc.tw, B * sc.Ncap, "scratch") ||
@@ -156,6 +156,8 @@ bool sgufp_ctx::init() {
         if (!alloc(sc.resume, B * kResumeWords, "scratch") || !alloc(sc.rgs, B * (size_t)(sc.Tcap + 1), "scratch")) return false;
         split_min = cus * relax_occupancy(sc.Tcap, sc.Lcap, cb, sc.us) * 3 / 2;
     }
+    if (const char *e = getenv("SGUFP_RELAX_TEMPLATES")) tpl_mode = atoi(e) != 0 ? 1 : 0;
+    if (cb > 1 && (tpl_mode == 1 || (tpl_mode < 0 && sc.resume)) && !tpl_init(held - held0)) return false;
     // per-slot refold diagnostics of the exact redos (sgufp_batch_refold_stats; off by default)
     if (const char *e = getenv("SGUFP_REFOLD_STATS"))
         if (atoi(e) != 0 && cb > 1 && !alloc(sc.rstat, B * kRefoldStats, "scratch")) return false;
@@ -444,6 +446,37 @@ bool sgufp_ctx::nx_prepare(int no) {
     return true;
 }
 
+// The template pool (Templates, dd_device.hpp): a second scratch view of K slots and the key table.
+bool sgufp_ctx::tpl_init(size_t scratch_bytes) {
+    Scratch &tp = tpl.tp;
+    tp = sc;
+    const size_t slot_bytes = (size_t)sc.Ncap * 13 + (size_t)sc.Acap * 5 + (size_t)sc.tmir_cap * 2 +
+                              (size_t)sc.Tcap * 22 + kResumeWords * 4 + 8 * 4 + 8 + 8;
+    int64_t K = std::max<int64_t>(16, (int64_t)(scratch_bytes / 20 / slot_bytes));
+    if (const char *e = getenv("SGUFP_RELAX_TEMPLATE_SLOTS")) K = std::max(1, atoi(e));
+    K = std::min<int64_t>(K, max_batch);   // a class has two records or more; s2 / tw alias the batch scratch
+    const size_t k = (size_t)K;
+    tp.rstat = nullptr;
+    // the byte and u16 arrays end in a padding word (copy_bytes reads whole words)
+    if (!alloc(tp.ntopo, k * sc.Ncap, "templates") || !alloc(tp.nflag, k * sc.Ncap + 4, "templates") ||
+        !alloc(tp.nmask, k * sc.Ncap, "templates") || !alloc(tp.outcnt, k * sc.Ncap, "templates") ||
+        !alloc(tp.atopo, k * sc.Acap, "templates") || !alloc(tp.aflag, k * sc.Acap + 4, "templates") ||
+        !alloc(tp.tmir, k * (size_t)sc.tmir_cap + 2, "templates") || !alloc(tp.lay, k * sc.Tcap * 5, "templates") ||
+        !alloc(tp.rgs, k * (size_t)(sc.Tcap + 1), "templates") || !alloc(tp.resume, k * kResumeWords, "templates") ||
+        !alloc(tp.meta, k * 8, "templates") || !alloc(tp.ubv, k, "templates") || !alloc(tpl.tkey, k, "templates") ||
+        !alloc(tpl.rec, (size_t)max_batch, "templates"))
+        return false;
+    tpl_table_cap = 64;
+    while (tpl_table_cap < 2 * max_batch) tpl_table_cap *= 2;
+    // counters, keys, counts and slot ids in one allocation: one memset zeroes them per relaxation
+    unsigned long long *tab = nullptr;
+    if (!alloc(tab, 2 + (size_t)tpl_table_cap * 2, "templates")) return false;
+    tpl.ctr = tab;
+    tpl.keys = tab + 2;
+    tpl.K = (int)K;
+    return true;
+}
+
 bool sgufp_ctx::split_prepare() {
     if (split_ready) return true;
     if (!hip_ok(hipEventCreateWithFlags(&split.fork, hipEventDisableTiming), "event")) return false;
@@ -471,8 +504,17 @@ bool sgufp_ctx::relax_current(double optimal_lb) {
     split.parts = split_parts;
     relax_launches = 0;
     split.launches = &relax_launches;
+    // templates where the batch splits by the rule (not by a forced SGUFP_RELAX_CHUNK alone)
+    tpl_used = tpl.K > 0 && (tpl_mode == 1 || (tpl_mode < 0 && do_split && in.n >= split_min));
+    if (tpl_used) {
+        tpl.table = 64;
+        while (tpl.table < 2 * in.n) tpl.table *= 2;
+        tpl.count = (uint32_t *)(tpl.keys + tpl.table);
+        tpl.tid = (int32_t *)(tpl.count + tpl.table);
+    }
     if (timing) hipEventRecord(ev[0], st);
-    if (!hip_ok(launch_relax(nd, sc, in, p, out, optimal_lb, cb, ex, cus, st, &split), "k_relax")) return false;
+    if (!hip_ok(launch_relax(nd, sc, in, p, out, optimal_lb, cb, ex, cus, st, &split, tpl_used ? &tpl : nullptr), "k_relax"))
+        return false;
     if (timing) hipEventRecord(ev[1], st);
     return emit_current(in, p);
 }
@@ -1454,6 +1496,17 @@ int sgufp_batch_refine(sgufp_ctx *ctx, int n, const int32_t *node_idx, const uin
                      "k_refine"))
         return SGUFP_ERR_HIP;
     return ctx->sync() ? SGUFP_OK : SGUFP_ERR_HIP;
+}
+
+int sgufp_relax_templates(sgufp_ctx *ctx, int64_t *built, int64_t *instantiated) {
+    if (!ctx || !built || !instantiated) return SGUFP_ERR_ARG;
+    *built = *instantiated = 0;
+    if (!ctx->tpl_used) return SGUFP_OK;
+    unsigned long long c[2] = {0, 0};
+    if (!ctx->download(c, ctx->tpl.ctr, 2) || !ctx->sync()) return SGUFP_ERR_HIP;
+    *built = (int64_t)std::min<unsigned long long>(c[0], (unsigned long long)ctx->tpl.K);
+    *instantiated = (int64_t)c[1];
+    return SGUFP_OK;
 }
 
 int sgufp_relax_launches(const sgufp_ctx *ctx, int64_t *launches) {

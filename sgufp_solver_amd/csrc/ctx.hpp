@@ -31,7 +31,7 @@ hipError_t launch_warm_pick(const SubIO &io, const WarmRing &wr, int ptr, hipStr
 hipError_t launch_flow_summary(int P, int S, int m, const int32_t *reward, int16_t *x, const uint8_t *ok,
                                double *flow_reward, double *mean_flow, hipStream_t st);
 hipError_t launch_relax(const NetDev &, const Scratch &, const BatchIn &, const Pool &, const BatchOut &, double, int,
-                        const ExactIO &, int, hipStream_t, const RelaxSplit *);
+                        const ExactIO &, int, hipStream_t, const RelaxSplit *, const Templates *);
 int relax_occupancy(int Tcap, int Lcap, int cb, int us);
 // exact_kernels.hip
 hipError_t launch_exact_cols(const double *rows, const double *rhs, const int32_t *o_order, int no, int first,
@@ -328,6 +328,18 @@ struct sgufp_ctx {
     bool split_ready = false;
     bool split_prepare();
     unsigned long long relax_launches = 0;    // k_relax launches of the last relaxation (sgufp_relax_launches)
+
+    // DD templates (Templates, dd_device.hpp): a relaxation that splits by the rule above (n >=
+    // split_min) builds every (g, mask) two or more of its eligible records share once and copies
+    // it; smaller batches keep their launches (at most one record per wave slot: a serial template
+    // build in front saves nothing).  SGUFP_RELAX_TEMPLATES=1 uses them for every batch with
+    // CB > 1, 0 never.  The pool holds tpl.K slots: what keeps it under 5 % of the scratch bytes, at
+    // least 16, at most max_batch; SGUFP_RELAX_TEMPLATE_SLOTS overrides the count.
+    Templates tpl{};
+    int tpl_mode = -1;                        // SGUFP_RELAX_TEMPLATES: -1 unset
+    int tpl_table_cap = 0;                    // key-table entries allocated
+    bool tpl_used = false;                    // the last relaxation ran with templates
+    bool tpl_init(size_t scratch_bytes);
 
     bool timing = false;
     hipEvent_t ev[4] = {};

@@ -137,6 +137,31 @@ struct RelaxSplit {
     unsigned long long *launches;
 };
 
+// DD templates of one relaxation (launch_relax).  What dd_build and
+// build_stream leave depends on the record's global layer and root state mask only, and the records
+// of a frontier share them massively, so a batch builds each (g, mask) that at least two of its
+// eligible records -- valid, not bound-pruned, sol_len == g -- carry once, into a slot of `tp`, and
+// k_relax copies the slot into the record's own scratch instead of building.  k_tpl_key groups the
+// records in an open-addressing table, k_tpl_assign hands the classes template slots (in no fixed
+// order: every member gets the same content whichever slot holds it; classes past K build
+// themselves), k_tpl_build builds them, one wave per slot.  `tp` has the shape of the batch scratch:
+// ntopo, nflag, nmask, outcnt, atopo, aflag, tmir, lay, rgs, meta and ubv of K slots are its own;
+// resume holds per slot T, exact, -, -, kg, Nn, Amir, ng, DD nodes / arcs / merged arcs, ok; s2, tw
+// and the single-cut summaries alias the batch scratch (the build's initial values land in record
+// slot t, whose own relaxation writes them again before it reads them), hence K <= max_batch.
+struct Templates {
+    int K;                                // template slots (0: no templates in this launch)
+    int table;                            // key-table entries in use: a power of two >= 2 n
+    unsigned long long SGUFP_GBL *ctr;    // [2] classes of two or more records, records instantiated
+    unsigned long long SGUFP_GBL *keys;   // [table] (g << 32 | mask) + 1, 0: empty
+    uint32_t SGUFP_GBL *count;            // [table] records carrying the key
+    int32_t SGUFP_GBL *tid;               // [table] template slot + 1, 0: none
+    int32_t SGUFP_GBL *rec;               // [max_batch] table entry of each record, -1: not eligible
+    unsigned long long SGUFP_GBL *tkey;   // [K] g << 32 | mask of each template slot
+    Scratch tp;
+};
+constexpr int kTplOk = 11;                // Scratch::resume word of a template slot: 1 = usable
+
 // Staged batch of open nodes (Inavap::Node records, DD.h:456-478), SoA.
 struct BatchIn {
     int n;

@@ -1840,6 +1840,98 @@ __device__ __forceinline__ void store_meta_layers(const DD &d, const Scratch &sc
     }
 }
 
+// ------------------------------------------------------------------------------------
+// DD templates (Templates, dd_device.hpp): streaming copies of a template slot into a record's
+// slot.  Global memory takes 16-byte accesses at 4-byte alignment, so the u32 arrays go as four
+// words per lane whatever the slot bases are; byte arrays are peeled to the destination's word
+// alignment and, where source and destination then disagree, realigned in registers.
+typedef uint32_t u32x4a __attribute__((ext_vector_type(4), aligned(4)));
+typedef double f64x2a __attribute__((ext_vector_type(2), aligned(8)));
+constexpr int kCopyUnroll = 4;   // 16-byte loads in flight per lane
+
+__device__ __forceinline__ void copy_words(GBL uint32_t *__restrict__ dst, const GBL uint32_t *__restrict__ src, uint32_t n) {
+    const uint32_t n4 = n >> 2;
+    GBL u32x4a *d4 = (GBL u32x4a *)dst;
+    const GBL u32x4a *s4 = (const GBL u32x4a *)src;
+    for (uint32_t base = 0; base < n4; base += kCopyUnroll * kWave) {
+        u32x4a v[kCopyUnroll];
+#pragma unroll
+        for (int u = 0; u < kCopyUnroll; u++) {
+            const uint32_t i = base + (uint32_t)u * kWave + (uint32_t)lane();
+            if (i < n4) v[u] = s4[i];
+        }
+#pragma unroll
+        for (int u = 0; u < kCopyUnroll; u++) {
+            const uint32_t i = base + (uint32_t)u * kWave + (uint32_t)lane();
+            if (i < n4) d4[i] = v[u];
+        }
+    }
+    for (uint32_t i = (n4 << 2) + (uint32_t)lane(); i < n; i += kWave) dst[i] = src[i];
+}
+// n bytes; the realigning path reads whole source words, up to 3 bytes past src + n (the template
+// pool's arrays end in a padding word)
+__device__ __forceinline__ void copy_bytes(GBL uint8_t *__restrict__ dst, const GBL uint8_t *__restrict__ src, uint32_t n) {
+    const uint32_t head = min(n, (uint32_t)(-(uintptr_t)dst & 3u));
+    if ((uint32_t)lane() < head) dst[lane()] = src[lane()];
+    const uint32_t nw = (n - head) >> 2;
+    GBL uint32_t *dw = (GBL uint32_t *)(dst + head);
+    const uint32_t sh = (uint32_t)((uintptr_t)(src + head) & 3u);
+    if (sh == 0) {
+        copy_words(dw, (const GBL uint32_t *)(src + head), nw);
+    } else {
+        const GBL uint32_t *sw = (const GBL uint32_t *)(src + head - sh);
+#pragma unroll kCopyUnroll
+        for (uint32_t i = lane(); i < nw; i += kWave) dw[i] = __builtin_amdgcn_alignbyte(sw[i + 1], sw[i], sh);
+    }
+    const uint32_t done = head + (nw << 2);
+    if ((uint32_t)lane() < n - done) dst[done + lane()] = src[done + lane()];
+}
+__device__ __forceinline__ void fill_f64(GBL double *dst, uint32_t n, double x) {
+    const uint32_t n2 = n >> 1;
+    GBL f64x2a *d2 = (GBL f64x2a *)dst;
+    const f64x2a v = {x, x};
+    for (uint32_t i = lane(); i < n2; i += kWave) d2[i] = v;
+    if ((n & 1u) && lane() == 0) dst[n - 1] = x;
+}
+
+// The record's DD from template slot t, in place of dd_build + build_stream: the layer table, the
+// staging groups and the scalars into LDS / registers, the node, arc and packed-topology ranges the
+// build wrote into the record's slot, s2 = DOUBLE_MIN, tw = DOUBLE_MAX on the last layer.  Leaves
+// the slot's scratch and the wave's state as the record's own build does.  false: the template
+// is not usable (its build ran out of capacity or found no staging groups); nothing was written.
+__device__ __forceinline__ bool dd_instantiate(DD &d, const Templates &tpl, int t, uint32_t &n_nodes, uint32_t &n_arcs,
+                                               uint32_t &n_merged) {
+    const Scratch &tp = tpl.tp;
+    const GBL int32_t *tw = tp.resume + (size_t)t * kResumeWords;
+    if (!uni(tw[kTplOk])) return false;
+    d.T = uni(tw[0]); d.exact = uni(tw[1]);
+    d.kg = uni(tw[4]); d.Nn = (uint32_t)uni(tw[5]); d.Amir = (uint32_t)uni(tw[6]); d.ng = uni(tw[7]);
+    n_nodes = (uint32_t)uni(tw[8]); n_arcs = (uint32_t)uni(tw[9]); n_merged = (uint32_t)uni(tw[10]);
+    const GBL uint32_t *lay = tp.lay + (size_t)t * tp.Tcap * 5;
+    for (int k = lane(); k < d.T; k += kWave) {
+        d.noff[k] = lay[k]; d.nn[k] = lay[tp.Tcap + k]; d.nalive[k] = lay[2 * tp.Tcap + k];
+        d.aoff[k] = lay[3 * tp.Tcap + k]; d.acnt[k] = lay[4 * tp.Tcap + k];
+    }
+    const GBL uint16_t *gs = tp.rgs + (size_t)t * (tp.Tcap + 1);
+    for (int k = lane(); k <= d.ng; k += kWave) d.gstart[k] = gs[k];
+    const size_t N = (size_t)t * tp.Ncap, A = (size_t)t * tp.Acap;
+    const uint32_t nodes = n_nodes - 1;   // without the terminal
+    copy_words(d.ntopo, tp.ntopo + N, nodes);
+    copy_words(d.nmask, tp.nmask + N, nodes);
+    copy_words(d.outcnt, tp.outcnt + N, nodes);
+    copy_words(d.atopo, tp.atopo + A, n_merged);
+    copy_bytes((GBL uint8_t *)d.tmir, (const GBL uint8_t *)(tp.tmir + (size_t)t * tp.tmir_cap), 2u * (d.Nn + d.Amir));
+    copy_bytes(d.nflag, tp.nflag + N, nodes);
+    copy_bytes(d.aflag, tp.aflag + A, n_merged);
+    fill_f64(d.s2, nodes, DMIN);
+    wave_lds_sync();
+    const uint32_t lo = uni(d.noff[d.T - 1]), ln = uni(d.nn[d.T - 1]);
+    for (uint32_t i = lane(); i < ln; i += kWave) d.tw[lo + i] = DMAX;
+    d.stream = 1;
+    wave_mem_sync();
+    return true;
+}
+
 // exact DD: argmax terminal arc (strict >, first wins) then the path of its tail
 __device__ __forceinline__ int dd_solution_path(const NetDev &net, DD &d, const GBL double *row, GBL int16_t *out_path,
                                 const GBL int16_t *rsol) {
@@ -2572,7 +2664,7 @@ __device__ __forceinline__ void relax_batch_view(BatchView &bv, LDS uint8_t *sme
 // MODE (dd_device.hpp, RelaxPart): the whole record, or one launch of a split relaxation.
 template <int CB, int MODE = kRelaxWhole>
 __global__ void __launch_bounds__(kWave, 2) k_relax(NetDev net, Scratch sc, BatchIn in, Pool pool, BatchOut out,
-                                                double incumbent, ExactIO ex, RelaxPart part) {
+                                                double incumbent, ExactIO ex, RelaxPart part, Templates tpl) {
     static_assert(MODE == kRelaxWhole || CB > 1, "only the batched loop suspends");
     extern __shared__ __attribute__((aligned(16))) uint8_t smem_raw[];
     LDS uint8_t *smem = (LDS uint8_t *)smem_raw;
@@ -2613,6 +2705,7 @@ __global__ void __launch_bounds__(kWave, 2) k_relax(NetDev net, Scratch sc, Batc
     int nx_k0 = -1;
     d.T = 1; d.exact = 1;
     LoopResume rs{0, false, false, pool.nf, false};
+    bool copied = false;   // the DD came from a template
 
     if constexpr (chunk) {
         // restore what the suspending launch saved (see the suspension below), then go on
@@ -2671,7 +2764,18 @@ __global__ void __launch_bounds__(kWave, 2) k_relax(NetDev net, Scratch sc, Batc
         }
         d.rslot[t] = (int16_t)s;
     }
-    if (!dd_build(net, d, sc, in.mask[slot], n_nodes, n_arcs, n_merged)) {
+    // a record of a class with a template takes the template's DD (Templates, dd_device.hpp)
+    if (CB > 1 && !chunk && tpl.K > 0 && d.aligned) {
+        const int e = uni(tpl.rec[slot]);
+        const int t = e >= 0 ? uni(tpl.tid[e]) - 1 : -1;
+        if (t >= 0) {
+            d.tmir = sc.tmir + (size_t)slot * sc.tmir_cap;
+            d.gstart = (LDS uint16_t *)(smem + lds_carve(sc.Tcap, sc.Lcap, CB, sc.us).o_gs);
+            copied = dd_instantiate(d, tpl, t, n_nodes, n_arcs, n_merged);
+            if (copied && lane() == 0) atomicAdd(&tpl.ctr[1], 1ull);
+        }
+    }
+    if (!copied && !dd_build(net, d, sc, in.mask[slot], n_nodes, n_arcs, n_merged)) {
         st.status = kErrCapacity;
         goto done;
     }
@@ -2684,7 +2788,7 @@ __global__ void __launch_bounds__(kWave, 2) k_relax(NetDev net, Scratch sc, Batc
         d.gstart = (LDS uint16_t *)(smem + cv.o_gs);
         BatchView bv;
         relax_batch_view<CB>(bv, smem, cv, sc, slot);
-        build_stream(d, n_merged, CB * pool.ustride);   // tmir_cap = Ncap + Acap >= Nn + Amir
+        if (!copied) build_stream(d, n_merged, CB * pool.ustride);   // tmir_cap = Ncap + Acap >= Nn + Amir
         const bool nxtry = ex.enabled && ex.nx && !ex.redo && !d.exact && pool.no >= ex.nx_min;
         if (d.stream)
             cut_loop_batched<CB, MODE>(net, d, sc, bv, pool, incumbent, st, efast, nxtry ? &ex : nullptr, slot, &nx_k0, &rs);
@@ -3294,6 +3398,77 @@ __global__ void __launch_bounds__(kWave) k_nx_fin(NetDev net, Scratch sc, BatchI
 }
 
 // ------------------------------------------------------------------------------------
+// DD templates (Templates, dd_device.hpp).  The table and the counters are zero at k_tpl_key.
+// Key pass: one thread per record; an eligible record -- the tests of k_relax, in its order, plus
+// sol_len == g -- claims or joins the table entry of its key (linear probing: the table has at
+// least two entries per record, so a probe ends).
+__global__ void __launch_bounds__(256) k_tpl_key(NetDev net, BatchIn in, Templates tpl, int Lcap, double incumbent) {
+    const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (i >= in.n) return;
+    const int g = in.gl[i], len = in.sol_len[i];
+    int e = -1;
+    if (in.valid[i] && len == g && g <= net.L && len <= Lcap && !(in.bound_prune && in.ub[i] <= incumbent)) {
+        const unsigned long long key = (((unsigned long long)g << 32) | in.mask[i]) + 1ull;
+        const uint32_t m = (uint32_t)tpl.table - 1u;
+        uint32_t h = (uint32_t)((key * 0x9E3779B97F4A7C15ull) >> 32) & m;
+        for (;;) {
+            const unsigned long long old = atomicCAS(&tpl.keys[h], 0ull, key);
+            if (old == 0ull || old == key) break;
+            h = (h + 1u) & m;
+        }
+        atomicAdd(&tpl.count[h], 1u);
+        e = (int)h;
+    }
+    tpl.rec[i] = e;
+}
+// one thread per table entry: a class of two or more records takes the next template slot
+__global__ void __launch_bounds__(256) k_tpl_assign(Templates tpl) {
+    const int e = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (e >= tpl.table || tpl.count[e] < 2u) return;
+    const unsigned long long id = atomicAdd(&tpl.ctr[0], 1ull);
+    if (id >= (unsigned long long)tpl.K) return;
+    tpl.tid[e] = (int32_t)id + 1;
+    tpl.tkey[id] = tpl.keys[e] - 1ull;
+}
+// one wave per template slot, the LDS carve of k_relax at the cut-batch size cb: the build of an
+// aligned record of the slot's key, as k_relax runs it, into the slot
+__global__ void __launch_bounds__(kWave) k_tpl_build(NetDev net, Templates tpl, int cb, int ustride) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem_raw[];
+    LDS uint8_t *smem = (LDS uint8_t *)smem_raw;
+    const int t = (int)blockIdx.x;
+    const unsigned long long made = tpl.ctr[0];
+    if (t >= tpl.K || (unsigned long long)t >= made) return;
+    const Scratch &tp = tpl.tp;
+    const unsigned long long key = tpl.tkey[t];
+    DD d;
+    dd_bind(d, smem, tp, t, cb);
+    d.g = uni((int)(key >> 32));
+    d.len = d.g;
+    d.aligned = 1;
+    d.T = 1; d.exact = 1;
+    d.tmir = tp.tmir + (size_t)t * tp.tmir_cap;
+    d.gstart = (LDS uint16_t *)(smem + lds_carve(tp.Tcap, tp.Lcap, cb, tp.us).o_gs);
+    uint32_t n_nodes = 0, n_arcs = 0, n_merged = 0;
+    GBL int32_t *tw = tp.resume + (size_t)t * kResumeWords;
+    bool ok = dd_build(net, d, tp, (uint32_t)key, n_nodes, n_arcs, n_merged);
+    if (ok) {
+        build_stream(d, n_merged, cb * ustride);
+        ok = d.stream != 0;
+    }
+    if (ok) {
+        GBL uint16_t *gs = tp.rgs + (size_t)t * (tp.Tcap + 1);
+        for (int k = lane(); k <= d.ng; k += kWave) gs[k] = d.gstart[k];
+        store_meta_layers(d, tp, t, -1, kSuccess, 0, DMIN);
+        if (lane() == 0) {
+            tw[0] = d.T; tw[1] = d.exact; tw[2] = 0; tw[3] = 0;
+            tw[4] = d.kg; tw[5] = (int32_t)d.Nn; tw[6] = (int32_t)d.Amir; tw[7] = d.ng;
+            tw[8] = (int32_t)n_nodes; tw[9] = (int32_t)n_arcs; tw[10] = (int32_t)n_merged;
+        }
+    }
+    if (lane() == 0) tw[kTplOk] = ok ? 1 : 0;
+}
+
+// ------------------------------------------------------------------------------------
 // Exclusive scan of two u32 arrays into u64 offsets (n+1 entries), one 1024-thread block.
 __global__ void __launch_bounds__(1024) k_scan2(const uint32_t *a, const uint32_t *b, int n, uint64_t *oa,
                                                uint64_t *ob) {
@@ -3345,7 +3520,8 @@ int relax_occupancy(int Tcap, int Lcap, int cb, int us) {
 // again through events, with no host synchronisation.
 template <int CB>
 static hipError_t relax_split(const NetDev &net, const Scratch &sc, const BatchIn &in, const Pool &pool, const BatchOut &out,
-                              double incumbent, const ExactIO &ex, const RelaxSplit &sp, size_t lds, hipStream_t st) {
+                              double incumbent, const ExactIO &ex, const RelaxSplit &sp, size_t lds, hipStream_t st,
+                              const Templates &tpl) {
     const int parts = std::max(1, std::min(sp.parts, std::min(in.n, kRelaxMaxParts)));
     const int nchunk = pool.no > 0 ? (pool.no + sp.q - 1) / sp.q : 0;
     hipError_t e;
@@ -3357,11 +3533,11 @@ static hipError_t relax_split(const NetDev &net, const Scratch &sc, const BatchI
         BatchIn part = in;
         part.n = hi;
         hipLaunchKernelGGL((k_relax<CB, kRelaxHead>), dim3(hi - lo), dim3(kWave), lds, s, net, sc, part, pool, out, incumbent,
-                           ex, RelaxPart{lo, 0});
+                           ex, RelaxPart{lo, 0}, tpl);
         if (sp.launches) ++*sp.launches;
         for (int c = 0; c < nchunk; c++) {
             hipLaunchKernelGGL((k_relax<CB, kRelaxChunk>), dim3(hi - lo), dim3(kWave), lds, s, net, sc, part, pool, out,
-                               incumbent, ex, RelaxPart{lo, c + 1 < nchunk ? sp.q : 0});
+                               incumbent, ex, RelaxPart{lo, c + 1 < nchunk ? sp.q : 0}, Templates{});
             if (sp.launches) ++*sp.launches;
         }
         if ((e = hipGetLastError()) != hipSuccess) return e;
@@ -3374,23 +3550,36 @@ static hipError_t relax_split(const NetDev &net, const Scratch &sc, const BatchI
 
 hipError_t launch_relax(const NetDev &net, const Scratch &sc, const BatchIn &in, const Pool &pool,
                         const BatchOut &out, double incumbent, int cb, const ExactIO &ex, int cus, hipStream_t st,
-                        const RelaxSplit *sp) {
+                        const RelaxSplit *sp, const Templates *tp) {
     if (in.n <= 0) return hipSuccess;
     size_t lds = relax_lds_bytes(sc.Tcap, sc.Lcap, cb, sc.us);
     // k_relax at the cut-batch size cb (1, 4, 8 or 16; anything else runs single-cut)
-    auto relax = [&](const ExactIO &io) {
+    auto relax = [&](const ExactIO &io, const Templates &tpl) {
         const auto k = cb == 4 ? k_relax<4> : cb == 8 ? k_relax<8> : cb == 16 ? k_relax<16> : k_relax<1>;
-        hipLaunchKernelGGL(k, dim3(in.n), dim3(kWave), lds, st, net, sc, in, pool, out, incumbent, io, RelaxPart{0, 0});
+        hipLaunchKernelGGL(k, dim3(in.n), dim3(kWave), lds, st, net, sc, in, pool, out, incumbent, io, RelaxPart{0, 0},
+                           tpl);
         if (sp && sp->launches) ++*sp->launches;
         return hipGetLastError();
     };
     hipError_t e;
+    // DD templates, in front of every k_relax launch and on the caller's stream: zero the table and
+    // the counters (one allocation, ctr first), key pass, slot assignment, one build per slot
+    Templates tpl{};
+    if (tp && tp->K > 0 && (cb == 4 || cb == 8 || cb == 16)) {
+        tpl = *tp;
+        const size_t zero = 2 * sizeof(unsigned long long) + (size_t)tpl.table * (sizeof(unsigned long long) + 2 * sizeof(uint32_t));
+        if ((e = hipMemsetAsync((void *)tpl.ctr, 0, zero, st)) != hipSuccess) return e;
+        hipLaunchKernelGGL(k_tpl_key, dim3((in.n + 255) / 256), dim3(256), 0, st, net, in, tpl, sc.Lcap, incumbent);
+        hipLaunchKernelGGL(k_tpl_assign, dim3((tpl.table + 255) / 256), dim3(256), 0, st, tpl);
+        hipLaunchKernelGGL(k_tpl_build, dim3(tpl.K), dim3(kWave), lds, st, net, tpl, cb, pool.ustride);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+    }
     if (sp && sp->q > 0 && sc.resume && (cb == 4 || cb == 8 || cb == 16))
-        e = cb == 4 ? relax_split<4>(net, sc, in, pool, out, incumbent, ex, *sp, lds, st)
-          : cb == 8 ? relax_split<8>(net, sc, in, pool, out, incumbent, ex, *sp, lds, st)
-                    : relax_split<16>(net, sc, in, pool, out, incumbent, ex, *sp, lds, st);
+        e = cb == 4 ? relax_split<4>(net, sc, in, pool, out, incumbent, ex, *sp, lds, st, tpl)
+          : cb == 8 ? relax_split<8>(net, sc, in, pool, out, incumbent, ex, *sp, lds, st, tpl)
+                    : relax_split<16>(net, sc, in, pool, out, incumbent, ex, *sp, lds, st, tpl);
     else
-        e = relax(ex);
+        e = relax(ex, tpl);
     if (e != hipSuccess || !ex.enabled || ex.no <= 0) return e;
     // exact DDs handed off by k_relax: root folds, terminal weights, outcome
     if ((e = launch_exact(net, sc, ex, incumbent, cus, st)) != hipSuccess) return e;
@@ -3403,7 +3592,7 @@ hipError_t launch_relax(const NetDev &net, const Scratch &sc, const BatchIn &in,
     if ((e = hipGetLastError()) != hipSuccess) return e;
     ExactIO rx = ex;
     rx.redo = 1;
-    return relax(rx);
+    return relax(rx, Templates{});
 }
 
 hipError_t launch_scan(const uint32_t *a, const uint32_t *b, int n, uint64_t *oa, uint64_t *ob, hipStream_t st) {
@@ -3436,7 +3625,7 @@ hipError_t launch_dd_build(const NetDev &net, const Scratch &sc, const BatchIn &
     none.ustride = 1;
     ExactIO ex{};
     hipLaunchKernelGGL(k_relax<1>, dim3(in.n), dim3(kWave), relax_lds_bytes(sc.Tcap, sc.Lcap, 1, sc.us), st, net, sc,
-                       in, none, out, DMIN, ex, RelaxPart{0, 0});
+                       in, none, out, DMIN, ex, RelaxPart{0, 0}, Templates{});
     return hipGetLastError();
 }
 

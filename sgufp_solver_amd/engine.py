@@ -137,6 +137,8 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     lib.sgufp_batch_routes.argtypes = [P, P]
     if hasattr(lib, "sgufp_relax_launches"):   # (an older build named by SGUFP_LIB_PATH has none)
         lib.sgufp_relax_launches.argtypes = [P, P]
+    if hasattr(lib, "sgufp_relax_templates"):   # (likewise)
+        lib.sgufp_relax_templates.argtypes = [P, P, P]
     lib.sgufp_subproblem.argtypes = [P, C.c_int, P, P, P, P, P, P]
     lib.sgufp_subproblem_detail.argtypes = [P, P, P, P]
     lib.sgufp_slot_keys.argtypes = [P, P]
@@ -454,6 +456,13 @@ class Engine:
         v = C.c_int64(0)
         self._check(self.lib.sgufp_relax_launches(self.ctx, C.byref(v)))
         return int(v.value)
+
+    def relax_templates(self):
+        """(templates built, records instantiated from one) by the last relaxation
+        (sgufp_relax_templates): (0, 0) for a batch that ran without DD templates."""
+        b, i = C.c_int64(0), C.c_int64(0)
+        self._check(self.lib.sgufp_relax_templates(self.ctx, C.byref(b), C.byref(i)))
+        return int(b.value), int(i.value)
 
     def refold_stats(self):
         """Per record the refold counters of the last relaxation's exact redos

@@ -119,6 +119,24 @@ def main():
     if hasattr(eng.lib, "sgufp_relax_launches"):
         print(f"k_relax launches {eng.relax_launches()} (SGUFP_RELAX_CHUNK={os.environ.get('SGUFP_RELAX_CHUNK', 'default')}, "
               f"SGUFP_RELAX_STREAMS={os.environ.get('SGUFP_RELAX_STREAMS', 'default')})")
+    # census of the DD templates' classes (Templates, dd_device.hpp): eligible records -- valid, not
+    # bound-pruned (a staged batch prunes none), sol_len == gl -- by (g, mask, aligned)
+    # (the state set stands for the mask; BFS children are valid records)
+    sol_len = np.diff(fr.sol_off)
+    classes = {}
+    for k in range(fr.n):
+        if sol_len[k] == fr.gl[k] and st[k] != 16:
+            key = (int(fr.gl[k]), fr.states[fr.states_off[k]:fr.states_off[k + 1]].tobytes())
+            classes[key] = classes.get(key, 0) + 1
+    sizes = np.array(sorted(classes.values()), dtype=np.int64)
+    hist = {int(s): int(c) for s, c in zip(*np.unique(sizes, return_counts=True))}
+    shared = int(sizes[sizes >= 2].sum())
+    print(f"template census: {int(sizes.sum())} eligible of {fr.n} records, {len(sizes)} distinct (g, mask, aligned) keys, "
+          f"{shared} records ({100.0 * shared / max(1, fr.n):.1f} %) in classes >= 2; class size: classes {hist}")
+    if hasattr(eng.lib, "sgufp_relax_templates"):
+        built, copied = eng.relax_templates()
+        print(f"templates built {built}, records instantiated {copied} "
+              f"(SGUFP_RELAX_TEMPLATES={os.environ.get('SGUFP_RELAX_TEMPLATES', 'default')})")
     if args.dump:
         np.savez(args.dump, ticks=ticks, phases=eng.phases(), sweeps=sw, status=st, n_feas=16, n_opt=64,
                  ms_relax=ms_relax, nodes=args.nodes)
